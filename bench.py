@@ -16,7 +16,14 @@ from the batch mean as it drops flagged trajectories, which keeps theta finite (
 Scaling: by default the GLOBAL batch (--batch, 65,536 = BASELINE config 5) is split over the N ranks by
 shard_range ("scaling": "strong", 8,192 trajectories per GPU at N = 8); --weak keeps --batch per GPU.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--weak] [--no-cpu]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--weak] [--full] [--dump-outputs DIR]
+  A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the result line.  --full adds
+  every other measurement to the same line: the `steady_state` loop, the secondary legs (the other precision,
+  BASELINE configs 2-4, the receding driver), the weak-scaling leg at N > 1 and the CPU baseline; --no-steady,
+  --no-extra, --no-weak-leg and --no-cpu take single ones out of a --full run again.
+  --dump-outputs DIR: after the timed steps, what the last timed step left in the TubeMPC buffers a caller reads
+  (dump_outputs), as DIR/<name>.npy -- the same arguments give the same inputs, so two builds of the library can be
+  compared output for output.
   N > 1 without a torch.distributed environment: bench.py launches its N ranks itself (a child
   `python -m torch.distributed.run --nproc-per-node N ...` started before any GPU call, one process per
   GPU over RCCL) and exits with the child's status; under torchrun it is one rank.
@@ -376,6 +383,37 @@ def receding_leg(dev, dtype_name: str, B: int = 65536, H: int = 20, reps: int = 
             "roofline": roofline_of(algo, t, traffic, src, workload=wl, batch=B)}
 
 
+DUMP_MAX_TRAJ = 4096  # trajectories written by --dump-outputs (619 values each: ~10 MB in f32, ~20 MB in f64)
+
+
+def dump_outputs(mpc, out_dir: str, rank: int = 0, world: int = 1) -> dict:
+    """Write what the last step left in the buffers a TubeMPC caller reads, as out_dir/<name>.npy (N > 1:
+    <name>.rank<r>.npy, each rank its shard): the plant and nominal state (x, b, xbar, bbar), the nominal and
+    ancillary plans (Xnom, Unom, Xaux, Uaux), status and iters per trajectory, and the shared theta, vel and sums.
+    Floating arrays keep the run's precision (float32 / float64), the integer ones are written as float64.  A shard
+    of more than DUMP_MAX_TRAJ trajectories is written for a fixed sample of them (seeded, sorted; the trajectory
+    axis is the last one, and sample_index holds their global indices), which keeps the files under 64 MB in all.
+    Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize(mpc.device)
+    B = mpc.B
+    idx = np.arange(B) if B <= DUMP_MAX_TRAJ else np.sort(np.random.default_rng(0).choice(B, DUMP_MAX_TRAJ, replace=False))
+    sel = torch.as_tensor(idx, dtype=torch.int64, device=mpc.device)
+    per_traj = {"x": mpc.x, "b": mpc.b, "xbar": mpc.xbar, "bbar": mpc.bbar, "Xnom": mpc.Xnom, "Unom": mpc.Unom,
+                "Xaux": mpc.Xaux, "Uaux": mpc.Uaux, "status": mpc.status, "iters": mpc.iters}
+    arrays = {k: t.index_select(t.dim() - 1, sel) for k, t in per_traj.items()}
+    arrays.update(theta=mpc.theta, vel=mpc.vel, sums=mpc.sums)
+    arrays["sample_index"] = torch.as_tensor(idx + mpc.global_offset, dtype=torch.float64)
+    suffix = "" if world == 1 else f".rank{rank}"
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def _free_port() -> int:
     import socket
 
@@ -406,6 +444,11 @@ def main() -> None:
                     help="GLOBAL trajectories split over the ranks (strong scaling); per GPU with --weak")
     ap.add_argument("--weak", action="store_true", help="--batch trajectories per GPU (weak scaling)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the steady-state loop, the secondary legs, the weak-scaling leg (N > 1) "
+                         "and the CPU baseline; without it the run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU-baseline leg")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU/gloo rehearsal of launch, sharding and timing with a placeholder step (no GPU)")
@@ -420,6 +463,10 @@ def main() -> None:
                     help="nominal-ddp: print only the BASELINE config-2 line (one GPU); receding: only the receding "
                          "driver's leg (one GPU; profiling runs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.dry_run or args.workload != "tube"):
+        raise SystemExit("--dump-outputs writes the tube step's device buffers: not with --dry-run or another --workload")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -556,11 +603,14 @@ def main() -> None:
                  "wall_ms_per_step": float(g[4]), "overlap": bool(g[5]), "lanes": int(g[6])}
                 for g in (t.cpu() for t in gathered)]
 
-    # second field: the free-running Algorithm-2 loop -- one episode start, then warm-started steps t >= 1
+    # --dump-outputs: the buffers as the last timed step left them, before any further leg runs on this TubeMPC
+    dumped = dump_outputs(mpc, args.dump_outputs, rank, world) if args.dump_outputs else None
+
+    # second field (--full): the free-running Algorithm-2 loop -- one episode start, then warm-started steps t >= 1
     # (shifted warm starts, advanced plant, theta updated by the batch-mean gradient under the f32 health
     # policy of TubeMPC.grad_bound), K steps timed after W untimed ones
     steady = None
-    if not args.dry_run and not args.no_steady:
+    if args.full and not args.dry_run and not args.no_steady:
         mpc.reset(x0)
         for _ in range(max(args.warmup, 1)):
             mpc.step()
@@ -584,7 +634,7 @@ def main() -> None:
     # strong-scaling line (the per-GPU shard of the fixed global batch shrinks to 8,192 at N = 8, into the small-batch
     # regime) -- value = N x 65,536 x 31 / the slowest rank's step time
     weak = None
-    if world > 1 and not args.weak and not args.no_weak_leg:
+    if args.full and world > 1 and not args.weak and not args.no_weak_leg:
         Bw = 65536
         lo_w, hi_w = shard_range(Bw * world, rank, world)
         if args.dry_run:
@@ -660,9 +710,12 @@ def main() -> None:
                                 workload=None if args.dry_run else ("tube" if args.dtype == "f32" else "tube_f64"),
                                 batch=hi - lo),
     }
+    out["full"] = bool(args.full)
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     out["steady_state"] = steady
     out["weak_scaling"] = weak
-    if world == 1 and not args.dry_run and not args.no_extra:
+    if args.full and world == 1 and not args.dry_run and not args.no_extra:
         # secondary legs: the reference's configured precision (configs/dubins.yaml:8,
         # f64) on the same tube step, and BASELINE config 2 (batched nominal DDP, B = 4,096) in f32 / f64
         other = "f64" if args.dtype == "f32" else "f32"
@@ -684,7 +737,7 @@ def main() -> None:
         out["receding"] = {d: receding_leg(dev, d) for d in ("f32", "f64")}
     if args.dry_run:
         out["dry_run"] = True
-    if rank == 0 and not args.no_cpu and world == 1 and not args.dry_run:
+    if args.full and rank == 0 and not args.no_cpu and world == 1 and not args.dry_run:
         out["cpu_baseline"] = cpu_baseline(setup)
     else:
         out["cpu_baseline"] = None

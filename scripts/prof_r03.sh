@@ -17,7 +17,7 @@ run() {
   echo "[prof] rc=$rc"
   [ $rc -eq 0 ] || exit $rc
 }
-BENCH="bench.py --no-cpu --no-steady"
+BENCH="bench.py --full --no-cpu --no-steady"
 run rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- python3 $BENCH
 python3 scripts/trace_summary.py "$OUT/trace" "$OUT/trace_summary.json" --warmup 3 || exit 1
 SHORT="bench.py --steps 5 --warmup 1 --no-cpu --no-steady --no-extra"
@@ -28,6 +28,6 @@ run rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_I
 run rocprofv3 --pmc FETCH_SIZE -d "$OUT/cal_fetch" -o run --output-format csv -- python3 scripts/pmc_calib.py
 run rocprofv3 --pmc WRITE_SIZE -d "$OUT/cal_write" -o run --output-format csv -- python3 scripts/pmc_calib.py
 python3 scripts/pmc_summary.py "$OUT" "$OUT/pmc.json" --batch 65536 > /dev/null || exit 1
-timeout -k 10 300 python3 bench.py --no-cpu > "$OUT/bench.json.log" 2>&1 || exit 1
+timeout -k 10 300 python3 bench.py --full --no-cpu > "$OUT/bench.json.log" 2>&1 || exit 1
 tail -n 1 "$OUT/bench.json.log"
 echo "[prof] done"

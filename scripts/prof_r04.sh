@@ -44,6 +44,6 @@ pmc --pmc WRITE_SIZE -d "$OUT/f64/write" -o run --output-format csv -- python3 $
 pmc --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d "$OUT/f64/sq1" -o run --output-format csv -- python3 $B64
 cp -r "$OUT/cal_fetch" "$OUT/cal_write" "$OUT/f64/"
 python3 scripts/pmc_summary.py "$OUT/f64" "$OUT/f64/pmc.json" --batch 65536 --kernel fk64::tube_fast_kernel --workload tube_f64 > /dev/null || exit 1
-timeout -k 10 600 python3 bench.py --no-cpu > "$OUT/bench.json.log" 2>&1 || exit 1
+timeout -k 10 600 python3 bench.py --full --no-cpu > "$OUT/bench.json.log" 2>&1 || exit 1
 tail -n 1 "$OUT/bench.json.log"
 echo "[prof] done"

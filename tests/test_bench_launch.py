@@ -30,7 +30,7 @@ def _bench(*args, timeout=240):
 
 @pytest.mark.parametrize("n", [2, 8])
 def test_bench_self_launches_strong_scaling(n):
-    d = _bench("--gpus", str(n))
+    d = _bench("--gpus", str(n), "--full")  # --full: the weak-scaling leg beside the headline
     assert d["n_gpus"] == n
     assert d["scaling"] == "strong"
     assert d["config"]["global_batch"] == 65536
@@ -52,6 +52,16 @@ def test_bench_self_launches_strong_scaling(n):
     w = d["weak_scaling"]
     assert w["batch_per_gpu"] == 65536 and w["global_batch"] == 65536 * n
     assert abs(w["value"] - 65536 * n * 31 / (w["ms_per_step"] * 1e-3)) < 1e-6 * w["value"]
+
+
+def test_plain_run_is_the_headline_alone():
+    """Without --full the line keeps its headline fields and every further leg stays off (null)."""
+    d = _bench("--gpus", "2", "--steps", "3")
+    assert d["full"] is False and d["steps"] == 3
+    assert d["weak_scaling"] is None and d["steady_state"] is None and d["cpu_baseline"] is None
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert abs(d["value"] - 65536 * 31 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
 
 
 def test_bench_weak_scaling_flag():
