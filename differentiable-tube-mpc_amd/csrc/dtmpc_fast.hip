@@ -883,23 +883,36 @@ __device__ __forceinline__ real h_grad(const FP& p, real px, real py, real& gx, 
 // G0 (gamma = 0): b' = B(h(x')) -- the general form adds (-0) * (B(h(x)) - b), which changes nothing
 // for finite values
 // the Dubins part alone (fhat's first half, operation for operation)
+// ... with the heading's sin / cos given (dubins_sc) or evaluated here; fhat_sc hands the pair it evaluated out
+// (the sin / cos cache's writers, Scc below): the same operations in the same order either way
 template <class V>
-__device__ __forceinline__ void dubins(const FP& p, V& x0, V& x1, V& x2, V u0, V u1) {
+__device__ __forceinline__ void dubins_sc(const FP& p, V& x0, V& x1, V& x2, V u0, V u1, V sn, V cs) {
   DTMPC_NOCONTRACT
-  V sn, cs;
-  vsincos(x2, sn, cs);
   const V dv = p.dt * u0;
   x0 = ffma(dv, cs, x0);
   x1 = ffma(dv, sn, x1);
   x2 = ffma(V(p.dt), u1, x2);
 }
-template <int M, bool G0 = false, class V>
-__device__ __forceinline__ void fhat(const FP& p, V& x0, V& x1, V& x2, V& b, V u0, V u1, V& Bc) {
+template <class V>
+__device__ __forceinline__ void dubins(const FP& p, V& x0, V& x1, V& x2, V u0, V u1) {
   DTMPC_NOCONTRACT
-  dubins(p, x0, x1, x2, u0, u1);
+  V sn, cs;
+  vsincos(x2, sn, cs);
+  dubins_sc(p, x0, x1, x2, u0, u1, sn, cs);
+}
+template <int M, bool G0 = false, class V>
+__device__ __forceinline__ void fhat_sc(const FP& p, V& x0, V& x1, V& x2, V& b, V u0, V u1, V& Bc, V& sn, V& cs) {
+  DTMPC_NOCONTRACT
+  vsincos(x2, sn, cs);
+  dubins_sc(p, x0, x1, x2, u0, u1, sn, cs);
   const V Bn = vbarrier(p, h_sm<M>(p, x0, x1));
   b = G0 ? Bn : ffma(V(-p.gamma), Bc - b, Bn);
   Bc = Bn;
+}
+template <int M, bool G0 = false, class V>
+__device__ __forceinline__ void fhat(const FP& p, V& x0, V& x1, V& x2, V& b, V u0, V u1, V& Bc) {
+  V sn, cs;
+  fhat_sc<M, G0>(p, x0, x1, x2, b, u0, u1, Bc, sn, cs);
 }
 
 template <int M>
@@ -1001,9 +1014,31 @@ __device__ __forceinline__ V kdot(const f4& K, V e0, V e1, V e2, V e3) {
 // arithmetic -- the tube step's and the general path's ancillary solves, whose references are the nominal solve's
 // tape -- so the f32 line search may re-roll them instead of reading them (LS_RECOMP).  The standalone iLQR takes
 // any caller references (X_ref need not be a rollout of U_ref): RROLL = false, every reference row is read.
-template <bool TRACK, bool G0, bool RG0, int P, int NCV = NC, bool RROLL = true>
+// The sin / cos cache (SCC; f32, one lane per trajectory, gamma = 0 records): sin and cos of the CURRENT tape's heading
+// theta_k, k = 0..N-1, in the workgroup's LDS as sc[k][threadIdx.x] = (sin, cos) -- one ds_write_b64 / ds_read_b64 per
+// lane on consecutive 8-byte slots.  init_tape and the commit write the pair their scalar vsincos evaluates for the new
+// state of step k anyway; the next backward pass (lin_point) and the line search's and the commit's re-roll of the old
+// tape read it back instead of evaluating the same vsincos on the same bits again (~25 issue slots each at one wave
+// per SIMD).  A lane whose line search keeps its tape skips the commit, and its entries stay those of
+// the unchanged tape.  Every lane touches its own column only: no barrier.  The table is dynamic LDS of
+// N * 8 * blockDim bytes behind the kernel's static sums (launch_tube_fast sizes it and picks the instantiation).
+extern __shared__ f2 scc_tab[];
+template <bool ON>
+struct Scc {
+  unsigned lo, rs;  // this lane's byte offset in a row (threadIdx.x * 8), the row stride (blockDim.x * 8)
+  __device__ __forceinline__ f2* at(int k) const { return (f2*)((char*)scc_tab + ((unsigned)k * rs + lo)); }
+  __device__ __forceinline__ f2 ld(int k) const { return *at(k); }
+  __device__ __forceinline__ void st(int k, real sn, real cs) const { *at(k) = f2{sn, cs}; }
+};
+template <>
+struct Scc<false> {};
+
+template <bool TRACK, bool G0, bool RG0, int P, int NCV = NC, bool RROLL = true, bool SCC = false>
 struct Solve {
   static_assert(NCV == NC || (NCV == 4 && P != 4), "four lanes split six candidates");
+  static_assert(!SCC || (P == 1 && G0 && !DTMPC_FAST_F64), "the sin / cos cache: f32, one lane, gamma = 0 records");
+  static constexpr bool scc = SCC;  // the heading's sin / cos of the current tape in LDS (Scc)
+  Scc<SCC> sc;
   static constexpr bool rroll = RROLL;
   static constexpr bool g0 = G0;    // gamma = 0: the compact gain records (Gains)
   static constexpr bool ric0 = RG0; // gamma = 0: the Riccati step without the barrier state's zero column
@@ -1144,7 +1179,13 @@ __device__ __forceinline__ real init_tape(const FP& p, const FCost& c, const rea
     const real u0 = vclamp(v0, p.umin0, p.umax0), u1 = vclamp(v1, p.umin1, p.umax1);
     S.stu(k, f2{u0, u1});
     if (want_cost) J = J + stage<TRACK, Obs<M>::wrap>(c, s0, s1, s2, sb, u0, u1, R.x, R.y, R.z, Q.x, Q.y);
-    fhat<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc);
+    if constexpr (SV::scc) {  // sc[k] = sin / cos of theta_k, as this step evaluates them
+      real sn, cs;
+      fhat_sc<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc, sn, cs);
+      S.sc.st(k, sn, cs);
+    } else {
+      fhat<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc);
+    }
     S.stx(k + 1, f4{s0, s1, s2, sb});
   }
   if (!want_cost) return 0.f;
@@ -1466,6 +1507,15 @@ __device__ __forceinline__ Lin lin_point(const FP& p, const f4& X) {
   L.dB = dbarrier(p, h_grad<M>(p, X.x, X.y, L.gx, L.gy));
   return L;
 }
+// ... with the heading's (sin, cos) from the cache (Scc)
+template <int M>
+__device__ __forceinline__ Lin lin_point_sc(const FP& p, const f4& X, f2 sc) {
+  Lin L;
+  L.sn = sc.x;
+  L.cs = sc.y;
+  L.dB = dbarrier(p, h_grad<M>(p, X.x, X.y, L.gx, L.gy));
+  return L;
+}
 
 // backward pass (ilqr_backward, core/ddp.py:172-254).  P > 1: the per-point linearisation (sin / cos,
 // grad h, B' -- about a third of a step) is computed for P steps at once, one step per lane of the
@@ -1614,7 +1664,10 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
       const f4 X = nX, Rr = nR;
       const f2 V = nV, Q = nQ;
       next_inputs(k);
-      step(X, V, Rr, Q, k, lin_point<M>(p, X));
+      if constexpr (SV::scc)
+        step(X, V, Rr, Q, k, lin_point_sc<M>(p, X, S.sc.ld(k)));
+      else
+        step(X, V, Rr, Q, k, lin_point<M>(p, X));
     }
   } else {
     // lane h of the trajectory linearises row kt - h of each group of P steps kt, kt - 1, ...; the
@@ -2128,6 +2181,7 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
   // b is never needed (K's b column is zero at gamma = 0)
   constexpr bool RC = DTMPC_FAST_LS_RECOMP && SV::g0 && (!DTMPC_FAST_F64 || DTMPC_FAST64_RECOMP);
   constexpr bool RCR = RC && SV::rroll;  // the references re-rolled too (only when they are a device rollout)
+  static_assert(!SV::scc || RC, "the sin / cos cache serves the line search's re-roll of the old tape");
   real o0 = x0[0], o1 = x0[1], o2 = x0[2], q0 = 0.f, q1 = 0.f, q2 = 0.f;
   if (RCR && TRACK) {
     const f4 R0 = S.xr(0);
@@ -2135,12 +2189,17 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
     q1 = R0.y;
     q2 = R0.z;
   }
-  auto roll = [&](StepIn& L) {  // the tape's (and reference's) state of this step, then advance them
+  auto roll = [&](StepIn& L, int k) {  // the tape's (and reference's) state of step k, then advance them
     if (RC) {
       L.X0 = o0;
       L.X1 = o1;
       L.X2 = o2;
-      dubins(p, o0, o1, o2, L.V0, L.V1);
+      if constexpr (SV::scc) {  // the tape's sin / cos of theta_k from the cache (the references' are evaluated)
+        const f2 t = S.sc.ld(k);
+        dubins_sc(p, o0, o1, o2, L.V0, L.V1, t.x, t.y);
+      } else {
+        dubins(p, o0, o1, o2, L.V0, L.V1);
+      }
       if (TRACK && RCR) {
         L.r0 = q0;
         L.r1 = q1;
@@ -2157,22 +2216,22 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
   load_step<TRACK, !RC, SV, !RCR>(Bs, S, ix(1));
   for (int k = 0; k < N; k += 4) {
     load_step<TRACK, !RC, SV, !RCR>(Cs, S, ix(k + 2));
-    roll(A);
+    roll(A, k);
     ls_step<TRACK, M, NPR, SV::g0>(p, c, A, C, u0, u1);
     keep(k, u0, u1);
     if (k + 1 >= N) break;
     load_step<TRACK, !RC, SV, !RCR>(Ds, S, ix(k + 3));
-    roll(Bs);
+    roll(Bs, k + 1);
     ls_step<TRACK, M, NPR, SV::g0>(p, c, Bs, C, u0, u1);
     keep(k + 1, u0, u1);
     if (k + 2 >= N) break;
     load_step<TRACK, !RC, SV, !RCR>(A, S, ix(k + 4));
-    roll(Cs);
+    roll(Cs, k + 2);
     ls_step<TRACK, M, NPR, SV::g0>(p, c, Cs, C, u0, u1);
     keep(k + 2, u0, u1);
     if (k + 3 >= N) break;
     load_step<TRACK, !RC, SV, !RCR>(Bs, S, ix(k + 5));
-    roll(Ds);
+    roll(Ds, k + 3);
     ls_step<TRACK, M, NPR, SV::g0>(p, c, Ds, C, u0, u1);
     keep(k + 3, u0, u1);
   }
@@ -2183,12 +2242,12 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
   load_step<TRACK, !RC, SV, !RCR>(A, S, 0);
   load_step<TRACK, !RC, SV, !RCR>(Bs, S, N1 < 1 ? N1 : 1);
   for (int k = 0; k < N; k += 2) {
-    roll(A);
+    roll(A, k);
     ls_step<TRACK, M, NPR, SV::g0>(p, c, A, C, u0, u1);
     keep(k, u0, u1);
     load_step<TRACK, !RC, SV, !RCR>(A, S, uidx(k + 2 < N1 ? k + 2 : N1));
     if (k + 1 < N) {
-      roll(Bs);
+      roll(Bs, k + 1);
       ls_step<TRACK, M, NPR, SV::g0>(p, c, Bs, C, u0, u1);
       keep(k + 1, u0, u1);
       load_step<TRACK, !RC, SV, !RCR>(Bs, S, uidx(k + 3 < N1 ? k + 3 : N1));
@@ -2314,6 +2373,7 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
   // used: K's b column is zero) and saves 16 B per step of HBM reads.  (With gamma != 0 the re-roll would need
   // the barrier too, measured slower in round 2; f64 is instruction-bound: both read the old states.)
   constexpr bool CMR = DTMPC_FAST_CM_RECOMP && SV::g0 && (!DTMPC_FAST_F64 || DTMPC_FAST64_RECOMP);
+  static_assert(!SV::scc || CMR, "the sin / cos cache serves the commit's re-roll of the old tape");
   real o0 = s0, o1 = s1, o2 = s2;
   constexpr bool LX = !CMR;
   Solve<false, SV::g0, SV::ric0, SV::lanes> T0;  // no references needed
@@ -2324,7 +2384,14 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
   auto step = [&](const StepIn& cur, int k) {
     const real e0 = s0 - (CMR ? o0 : cur.X0), e1 = s1 - (CMR ? o1 : cur.X1), e2 = s2 - (CMR ? o2 : cur.X2);
     const real e3 = sb - cur.X3;  // CMR: unused (kdot<g0> drops the b column)
-    if (CMR) dubins(p, o0, o1, o2, cur.V0, cur.V1);
+    if (CMR) {
+      if constexpr (SV::scc) {  // the old tape's sin / cos of theta_k, read before this step writes the new pair
+        const f2 t = S.sc.ld(k);
+        dubins_sc(p, o0, o1, o2, cur.V0, cur.V1, t.x, t.y);
+      } else {
+        dubins(p, o0, o1, o2, cur.V0, cur.V1);
+      }
+    }
 #if DTMPC_FAST_KFMA
     const real du0 = cur.kk.x + kdot<SV::g0>(cur.Ka, e0, e1, e2, e3);
     const real du1 = cur.kk.y + kdot<SV::g0>(cur.Kb, e0, e1, e2, e3);
@@ -2339,7 +2406,13 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
     if (__builtin_isnan(s0 + u0 + u1)) S.stx(k + 1, f4{s0, s1, s2, sb});
 #else
     S.stu(k, f2{u0, u1});
-    fhat<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc);
+    if constexpr (SV::scc) {
+      real sn, cs;
+      fhat_sc<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc, sn, cs);
+      S.sc.st(k, sn, cs);
+    } else {
+      fhat<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc);
+    }
     S.stx(k + 1, f4{s0, s1, s2, sb});
 #endif
   };
@@ -2586,6 +2659,9 @@ __device__ __forceinline__ int sensitivity(const FP& p, const FCost& c, const SV
     const real x0 = X.x, x1 = X.y, x2 = X.z, xb = X.w;
     const real u0 = V.x, u1 = V.y;
     real sn, cs;
+    // (not from the sin / cos cache, though the final ancillary tape's pairs are in it: this pass compiles with implicit
+    // contraction, and without vsincos's range branch in the loop body the compiler fused its sums differently -- the
+    // tapes stayed bitwise equal, one gradient sum moved in its last bit; 50 of a step's ~4,500 evaluations)
     vsincos(x2, sn, cs);
     real gxk, gyk;
     const real dBk = dbarrier(p, h_grad<M>(p, x0, x1, gxk, gyk));
@@ -2813,12 +2889,13 @@ constexpr int tab_flag() {
              : 0;
 }
 
-// GM: 0 general, 1 gamma = 0 gain records, 2 gamma = 0 gain records + Riccati step (the default at gamma = 0)
+// GM: 0 general, 1 gamma = 0 gain records, 2 gamma = 0 gain records + Riccati step (the default at gamma = 0),
+// 3 (f32, one lane): 2 with the tape's heading sin / cos cached in dynamic LDS (Scc; launch_tube_fast's rule)
 // One wave per SIMD at every lane count (amdgpu_waves_per_eu(1, 1)): the whole 512-register budget.
 template <int M, int P, int GM>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1)))
 tube_fast_kernel(FK kk) {
-  constexpr bool G0 = GM > 0, RG0 = GM > 1;
+  constexpr bool G0 = GM > 0, RG0 = GM > 1, SCC = GM > 2;
   constexpr int ML = M | tab_flag<M, GM>() | xasm_flag<M, GM, P>();  // M with the table placement and exp form (f64)
   (void)kk;  // read through kargs()
   __shared__ f4 lds[kBlock / 64 * DTMPC_TUBE_SUMS / 4];  // the workgroup sums at the end
@@ -2866,7 +2943,8 @@ tube_fast_kernel(FK kk) {
     // the split step's hand-over (phase 1 -> 2): the nominal tape's final record offsets (P = 4: its slot) and
     // the nominal solve's status and iterations, [3][Bc] ints after the records
     int* const hand = (int*)((char*)kargs()->a.work + kargs()->a.oPH) + t;
-    Solve<false, G0, RG0, P> Sn;
+    Solve<false, G0, RG0, P, NC, true, SCC> Sn;
+    if constexpr (SCC) Sn.sc = Scc<true>{threadIdx.x * 8u, blockDim.x * 8u};
     if (phase == 2) {  // the nominal was solved by this step's phase-1 launch
       KArg* K = kargs();
       Sn.r = __builtin_amdgcn_make_buffer_rsrc(K->a.work, 0, (int)K->a.wsz, 0x00020000);
@@ -2912,7 +2990,8 @@ tube_fast_kernel(FK kk) {
       ca.qb = th[5];
       ca.tg = f4{0.f, 0.f, 0.f, 0.f};
     }
-    Solve<true, G0, RG0, P> Sa;
+    Solve<true, G0, RG0, P, NC, true, SCC> Sa;
+    if constexpr (SCC) Sa.sc = Sn.sc;  // the ancillary solve's start rollout fills the table again
     {  // ancillary MPC tracking the nominal plan (:863-909)
       KArg* K = kargs();
       Sa.r = __builtin_amdgcn_make_buffer_rsrc(K->a.work, 0, (int)K->a.wsz, 0x00020000);
@@ -3547,7 +3626,9 @@ static void fast_p(const dtmpc_spec* sp, FK_NS::FP& p) {
 #if DTMPC_FAST_ILP_SPLIT
 // the tube step's launches of the split units (dtmpc_fast_ilp.hip / dtmpc_fast64_ilp.hip): M obstacles, lanes 1 (or
 // 2 where DTMPC_FAST_ILP_P2), record form g0
-int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FK& kk);
+// (g0 = 3: the f32 one-lane form with the sin / cos cache, shm its table's bytes of dynamic LDS; else shm = 0)
+int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, unsigned shm, hipStream_t st,
+                              const FK_NS::FK& kk);
 #endif
 
 #ifndef DTMPC_FAST_AUX_TU  // the tube step (this file's own translation unit)
@@ -3612,6 +3693,27 @@ static int fast_g0(const dtmpc_spec* sp) {
     if ((e[0] == '0' || e[0] == '1') && e[1] == 0) g0 = g0 < e[0] - '0' ? g0 : e[0] - '0';
   return g0;
 }
+
+#if !DTMPC_FAST_F64
+// The sin / cos cache's launches (FK_NS::Scc, tube_fast_kernel<M, 1, 3>): a launch of Bc trajectories of a batch of B
+// takes the cached kernel when
+//   - it is the f32 one-lane form with the gamma = 0 records and recursion (g0 == 2), the form whose line search and
+//     commit re-roll the old tape;
+//   - the horizon's table fits: N <= kSccMaxN = 64, i.e. 64 * 8 * 256 = 128 KiB of the CU's 160 KiB at 256-thread
+//     workgroups, and four 64-thread workgroups' 32 KiB tables and static sums on one CU alike;
+//   - every workgroup of the launch is resident at once with its table: no more threads than the device has lane slots
+//     (CUs x 4 SIMDs x 64).  Above that the kernel runs in more than one round of workgroups, and a 256-thread
+//     workgroup's table (100 KiB at N = 50) would keep the second workgroup a CU could otherwise hold waiting.
+// DTMPC_FAST_SCC=0 (environment, read at each call) forces the kernel without the table (A/B, tests).
+constexpr int kSccMaxN = 64;
+static bool tube_fast_scc(int N, int64_t B, int64_t Bc, int lanes, int g0) {
+  if (const char* e = getenv("DTMPC_FAST_SCC"))
+    if (e[0] == '0' && e[1] == 0) return false;
+  if (lanes != 1 || g0 != 2 || N < 1 || N > kSccMaxN || Bc < 1) return false;
+  const int64_t bs = tube_block(B, lanes);
+  return (Bc + bs - 1) / bs * bs <= lane_slots();
+}
+#endif
 
 #if DTMPC_FAST_F64
 // f64 general gain records at four lanes.  Round 5 v2 ran them on the generic f64 kernel: the fused form gave
@@ -3706,13 +3808,27 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
     a.wsz = f.wsz;
     const int bs = tube_block(B, lanes);  // 64 while the batch leaves SIMDs idle: one wave per workgroup
     const dim3 grid = dim3((unsigned)((Bc * lanes + bs - 1) / bs));
-#define FAST_LAUNCH(m, l, g) hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), 0, st, kk)
+    // this launch's kernel form: g0, or 3 -- the sin / cos cache with its [N][bs] table of 8-byte pairs as dynamic LDS
+    int gk = g0;
+    unsigned shm = 0;
+#if !DTMPC_FAST_F64
+    if (tube_fast_scc(N, B, Bc, lanes, g0)) {
+      gk = 3;
+      shm = (unsigned)N * 8u * (unsigned)bs;
+    }
+#endif
+    (void)gk;
+#define FAST_LAUNCH(m, l, g) \
+  hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) == 3 ? shm : 0u, st, kk)
 #define FAST_LANES(m, l) \
   if (g0 == 2) FAST_LAUNCH(m, l, 2); else if (g0) FAST_LAUNCH(m, l, 1); else FAST_LAUNCH(m, l, 0);
 #ifdef DTMPC_FAST_ISA_ONLY  // ISA inspection builds: one instantiation (lanes 1, gamma = 0 records + Riccati)
+#ifndef DTMPC_FAST_ISA_GM
+#define DTMPC_FAST_ISA_GM 2  // 3: the sin / cos cache form (lanes 1)
+#endif
 #define FAST_CASE(m) \
   case m:            \
-    FAST_LAUNCH(m, DTMPC_FAST_ISA_ONLY, 2); break;
+    FAST_LAUNCH(m, DTMPC_FAST_ISA_ONLY, DTMPC_FAST_ISA_GM); break;
 #else
 #define FAST_CASE(m)                                                                                       \
   case m:                                                                                                  \
@@ -3727,13 +3843,16 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
 #endif
 #if DTMPC_FAST_ILP_SPLIT
 #define FAST_LANES_P1(m) \
-  if (int r = FKN(launch_tube_fast_ilp)(m, 1, g0, grid, bs, st, kk)) return r;
-#else
+  if (int r = FKN(launch_tube_fast_ilp)(m, 1, gk, grid, bs, shm, st, kk)) return r;
+#elif DTMPC_FAST_F64
 #define FAST_LANES_P1(m) FAST_LANES(m, 1)
+#else
+#define FAST_LANES_P1(m) \
+  if (gk == 3) FAST_LAUNCH(m, 1, 3); else { FAST_LANES(m, 1) }
 #endif
 #if DTMPC_FAST_ILP_P2
 #define FAST_LANES_P2(m) \
-  if (int r = FKN(launch_tube_fast_ilp)(m, 2, g0, grid, bs, st, kk)) return r;
+  if (int r = FKN(launch_tube_fast_ilp)(m, 2, g0, grid, bs, 0u, st, kk)) return r;
 #else
 #define FAST_LANES_P2(m) FAST_LANES(m, 2)
 #endif
@@ -3757,26 +3876,35 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
 #elif defined(DTMPC_FAST_ILP_TU)  // the split units' tube kernels (csrc/dtmpc_fast_ilp.hip, dtmpc_fast64_ilp.hip)
 
 #if DTMPC_FAST_ILP_SPLIT
-int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FK& kk) {
-#define ILP_LAUNCH(m, l, g) hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), 0, st, kk)
+int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, unsigned shm, hipStream_t st,
+                              const FK_NS::FK& kk) {
+#define ILP_LAUNCH(m, l, g) \
+  hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) == 3 ? shm : 0u, st, kk)
 #define ILP_LANES(m, l) \
   if (g0 == 2) ILP_LAUNCH(m, l, 2); else if (g0) ILP_LAUNCH(m, l, 1); else ILP_LAUNCH(m, l, 0);
+#if DTMPC_FAST_F64
+#define ILP_LANES1(m) ILP_LANES(m, 1)
+#else  // f32 at one lane: g0 = 3 is the sin / cos cache form
+#define ILP_LANES1(m) \
+  if (g0 == 3) ILP_LAUNCH(m, 1, 3); else { ILP_LANES(m, 1) }
+#endif
 #if DTMPC_FAST_ILP_P2
 #define ILP_CASE(m)         \
   case m:                   \
     if (lanes == 2) {       \
       ILP_LANES(m, 2)       \
     } else {                \
-      ILP_LANES(m, 1)       \
+      ILP_LANES1(m)         \
     }                       \
     return 0;
 #else
 #define ILP_CASE(m) \
   case m:           \
-    ILP_LANES(m, 1) \
+    ILP_LANES1(m)   \
     return 0;
 #endif
   if (lanes != 1 && !(DTMPC_FAST_ILP_P2 && lanes == 2)) return set_err(DTMPC_ERR_BAD_ARG, "split tube unit: lanes");
+  if (g0 == 3 && (lanes != 1 || DTMPC_FAST_F64)) return set_err(DTMPC_ERR_BAD_ARG, "split tube unit: sin / cos cache form");
   switch (M) {
 #ifdef DTMPC_FAST_M_ONLY
     ILP_CASE(DTMPC_FAST_M_ONLY)
@@ -3786,6 +3914,7 @@ int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, 
     default: return set_err(DTMPC_ERR_BAD_ARG, "fast tube step: obstacle count not instantiated");
   }
 #undef ILP_CASE
+#undef ILP_LANES1
 #undef ILP_LANES
 #undef ILP_LAUNCH
 }
@@ -4052,6 +4181,16 @@ int FKN(launch_general_solve_fast)(const dtmpc_spec* sp, const dtmpc_general_cfg
 
 #if !defined(DTMPC_FAST_AUX_TU) && !DTMPC_FAST_F64
 extern "C" {
+// diagnostics (not part of include/dtmpc.h): 1 when every launch of an f32 tube step of B trajectories in chunks of
+// `chunk` (dtmpc_tube_chunk) at `lanes` takes the sin / cos cache kernel (tube_fast_scc: the rule and its switch), else 0
+int dtmpc_diag_tube_sincos_cache(int dtype, int32_t horizon, int64_t B, int64_t chunk, int32_t lanes, double dbas_gamma) {
+  if (dtype != DTMPC_F32 || horizon < 1 || B < 1 || chunk < 1 || (lanes != 1 && lanes != 2 && lanes != 4)) return 0;
+  dtmpc_spec sp;
+  std::memset(&sp, 0, sizeof(sp));
+  sp.dbas_gamma = dbas_gamma;
+  const int64_t cmax = dtmpc::tube_fast_chunk_max(horizon, lanes), c = chunk < cmax ? chunk : cmax;
+  return dtmpc::tube_fast_scc(horizon, B, B < c ? B : c, lanes, dtmpc::fast_g0(&sp)) ? 1 : 0;
+}
 // diagnostics (not part of include/dtmpc.h): the counter-calibration copy of record_stream_kernel over
 // src / dst buffers of (N+1) x 16 + N x 8 bytes per trajectory (< 2^31 bytes)
 int dtmpc_diag_record_stream(int64_t B, int32_t N, const void* src, void* dst, void* stream) {

@@ -175,6 +175,8 @@ inline dim3 grid_for(int64_t B) { return dim3((unsigned)((B + kBlock - 1) / kBlo
 // partial-sum rows are per workgroup: dtmpc_tube_partials_count follows this rule.
 // -D DTMPC_TUBE_SMALL_BLOCK=0: always 256 (A/B builds).
 int tube_block(int64_t B, int lanes);
+// the device's lane slots, CUs x 4 SIMDs x 64 (without a device the MI355X's 65,536): one lane per slot is one wave per SIMD
+int64_t lane_slots();
 
 // the specialised tube step of the paper configuration (dtmpc_fast.hip)
 bool tube_fast_eligible(int dtype, const dtmpc_spec* sp, const dtmpc_tube_cfg* cf);

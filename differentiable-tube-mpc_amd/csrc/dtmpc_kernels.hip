@@ -242,7 +242,7 @@ struct TubeArgs {
 // kernel runs a 4-lane state with LPT = 2.  DTMPC_TUBE_LANES=1|2|4 (environment) forces a count, for
 // the parity tests; it is read by dtmpc_tube_lanes only, i.e. once, when the caller builds its state
 // (state->lanes).  Without a device (host-side tests) the MI355X count is assumed.
-static int64_t lane_slots() {
+int64_t lane_slots() {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
       cus <= 0) {
