@@ -57,15 +57,11 @@ __device__ __forceinline__ void sincos_cw(float x, float* sp, float* cp) {
   *cp = ((j + 1) & 2) ? -co : co;
 }
 __device__ __forceinline__ void m_sincos(float x, float* s, float* c) {
-#ifdef DTMPC_OCML_SINCOS
-  sincosf(x, s, c);
-#else
   if (__builtin_expect(!(__builtin_fabsf(x) <= 65536.0f), 0)) {
     sincosf(x, s, c);
     return;
   }
   sincos_cw(x, s, c);
-#endif
 }
 __device__ __forceinline__ void m_sincos(double x, double* s, double* c) { sincos(x, s, c); }
 __device__ __forceinline__ float m_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }

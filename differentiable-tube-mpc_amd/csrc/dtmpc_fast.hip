@@ -97,80 +97,50 @@ constexpr int kTight = 16;
 // kWrap: the nominal target cost with the heading error wrapped to (-pi, pi] (run_nominal.py:297-324, the
 // receding-horizon driver's stage / terminal cost and derivatives); only the receding kernel sets it.
 constexpr int kWrap = 32;
-// kLds (f64): the obstacle table read again at each use instead of being held in registers -- the f64
-// instantiations whose table cannot be pinned in VGPRs without spilling (tab_flag below).  DTMPC_FAST64_TABSRC:
-// 1 (default) a scalar load of the kernarg segment's copy (every kernel's arguments start with its FP); 0 the
-// workgroup's LDS copy (obs_lds; A/B: at four lanes its even-M general-record kernels gave run-to-run
-// different results).
-constexpr int kLds = 64;
+// kReread (f64): the obstacle table read again at each use instead of being held in registers -- the f64
+// instantiations whose table cannot be pinned in VGPRs without spilling (tab_flag below).  Each use is a scalar
+// load of the kernarg segment's copy (every kernel's arguments start with its FP); a workgroup LDS copy gave
+// run-to-run different results at four lanes in the even-M general-record kernels.
+constexpr int kReread = 64;
 // kXasm (f64): the smooth-min exp's polynomial as one inline-assembly block (exp_sm<true>) -- set only where it
 // fits the register file without a private segment (xasm_flag below); elsewhere the same fmas compiled normally.
 constexpr int kXasm = 128;
-#ifndef DTMPC_FAST64_TABSRC
-#define DTMPC_FAST64_TABSRC 1
-#endif
 template <int M>
 struct Obs {
   static constexpr int n = M & (kTight - 1);
   static constexpr bool tight = (M & kTight) != 0;
   static constexpr bool wrap = (M & kWrap) != 0;
-  static constexpr bool lds = (M & kLds) != 0;
+  static constexpr bool reread = (M & kReread) != 0;
   static constexpr bool xasm = (M & kXasm) != 0;
 };
 
-#if DTMPC_FAST_F64 && DTMPC_FAST64_TABSRC == 0
-// the f64 kernels' obstacle table in LDS (x, y, r^2, -) per obstacle, written once per workgroup (obs_fill)
-__shared__ real obs_lds[32];
-#endif
-// obstacle i of the table: the registers of FP, or (kLds) loaded again at each use -- through an opaque pointer
-// (a hoisted load would hold the table in registers for the whole loop, which is what kLds instantiations cannot
+// obstacle i of the table: the registers of FP, or (kReread) loaded again at each use -- through an opaque pointer
+// (a hoisted load would hold the table in registers for the whole loop, which is what kReread instantiations cannot
 // afford): a scalar load from the kernarg segment (the value is wave-uniform, so it lands in an SGPR pair for the
-// few instructions that use it), or the LDS copy
+// few instructions that use it)
 template <int M>
 __device__ __forceinline__ real otab_at(int f, int i) {
-#if DTMPC_FAST_F64 && DTMPC_FAST64_TABSRC == 0
-  return ((volatile __attribute__((address_space(3))) real*)obs_lds)[4 * i + f];
-#else
   // kernarg FP: cx at offsetof(FP, cx), cy, r2 follow (f8 each); the pointer made opaque per use
   typedef __attribute__((address_space(4))) const real creal;
   creal* k = (creal*)((__attribute__((address_space(4))) const char*)__builtin_amdgcn_kernarg_segment_ptr() +
                       offsetof(FP, cx) + (unsigned)f * sizeof(f8));
   __asm__ volatile("" : "+s"(k));
   return k[i];
-#endif
 }
 template <int M>
 __device__ __forceinline__ real ocx(const FP& p, int i) {
-  if (DTMPC_FAST_F64 && Obs<M>::lds) return otab_at<M>(0, i);
+  if (DTMPC_FAST_F64 && Obs<M>::reread) return otab_at<M>(0, i);
   return p.cx[i];
 }
 template <int M>
 __device__ __forceinline__ real ocy(const FP& p, int i) {
-  if (DTMPC_FAST_F64 && Obs<M>::lds) return otab_at<M>(1, i);
+  if (DTMPC_FAST_F64 && Obs<M>::reread) return otab_at<M>(1, i);
   return p.cy[i];
 }
 template <int M>
 __device__ __forceinline__ real or2(const FP& p, int i) {
-  if (DTMPC_FAST_F64 && Obs<M>::lds) return otab_at<M>(2, i);
+  if (DTMPC_FAST_F64 && Obs<M>::reread) return otab_at<M>(2, i);
   return p.r2[i];
-}
-// kLds kernels: the table into LDS from the kernarg copy, before any lane returns (one barrier)
-template <int M>
-__device__ __forceinline__ void obs_fill(const FP& p) {
-#if DTMPC_FAST_F64 && DTMPC_FAST64_TABSRC == 0
-  if (Obs<M>::lds) {
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        obs_lds[4 * j] = p.cx[j];
-        obs_lds[4 * j + 1] = p.cy[j];
-        obs_lds[4 * j + 2] = p.r2[j];
-        obs_lds[4 * j + 3] = 0.0;
-      }
-    }
-    __syncthreads();
-  }
-#endif
 }
 
 struct FCost {  // nominal: target; ancillary: tracking (terminal weight = stage weight)
@@ -293,53 +263,28 @@ struct RA {
   unsigned base, rs, lo;  // uniform base and row stride (bytes), per-lane offset (bytes)
   __device__ __forceinline__ unsigned so(int k) const { return base + (unsigned)k * rs; }
 };
-#ifndef DTMPC_FAST_STPOL
-#define DTMPC_FAST_STPOL 0  // cache-policy bits of the record stores (A/B)
-#endif
 // 128-bit buffer stores and the gfx950 store-data hazard (round 5).  A buffer_store_dwordx4 reads its data VGPRs
 // after issue; a VALU write to them in the next cycles changes what the store writes.  The compiler pads this hazard
 // only for stores without an SGPR soffset, and every record store here has one (the row base): it emitted a
 // dwordx4 store followed at once by a move into its data registers, and the store wrote the moved value
-// (profiles/r05/store_hazard.txt: one component of one record, a reproducible wrong tape).  DTMPC_FAST_STNOP = 1
-// (default): every 128-bit record store is followed by an s_nop 1 that reads its data registers, so they stay
-// unwritten for its two wait states.  Stores of 64 bits and less are not affected.
-#ifndef DTMPC_FAST_STNOP
-#define DTMPC_FAST_STNOP 1
-#endif
+// (profiles/r05/store_hazard.txt: one component of one record, a reproducible wrong tape).  So every 128-bit record
+// store is followed by an s_nop 1 that reads its data registers: they stay unwritten for its two wait states.
+// Stores of 64 bits and less are not affected.
 template <class D>
 __device__ __forceinline__ void st128(D d, Rsrc r, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, d), r, voff, soff, DTMPC_FAST_STPOL);
-#if DTMPC_FAST_STNOP
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, d), r, voff, soff, 0);
   __asm__ volatile("s_nop 1" ::"v"(d));
-#endif
 }
 #if DTMPC_FAST_F64
 // f64: a 4-value row is 32 bytes (two 16-byte accesses), a 2-value row 16 bytes (one)
 typedef double d2v __attribute__((ext_vector_type(2)));
-#ifdef DTMPC_DIAG_STALE
-// diagnostics builds (scripts/diag_stale.py): a workspace pre-filled with 0xff bytes holds the all-ones pattern, which
-// no arithmetic produces (a computed NaN is 0x7ff8...): a record load that returns it read a slot this run never wrote
-__device__ __noinline__ void stale_hit(unsigned base, unsigned so, unsigned vo, int which) {
-  printf("STALE blk=%d thr=%d base=%u soff=%u voff=%u part=%d\n", (int)blockIdx.x, (int)threadIdx.x, base, so, vo, which);
-}
-__device__ __forceinline__ void stale_chk(d2v v, const RA& a, int k, unsigned off, int which) {
-  const unsigned long long ones = ~0ull;
-  if (__builtin_bit_cast(unsigned long long, v.x) == ones || __builtin_bit_cast(unsigned long long, v.y) == ones)
-    stale_hit(a.base, a.so(k), a.lo + off, which);
-}
-#else
-__device__ __forceinline__ void stale_chk(d2v, const RA&, int, unsigned, int) {}
-#endif
 __device__ __forceinline__ f4 rld4(Rsrc r, const RA& a, int k, unsigned off) {
   const d2v lo = __builtin_bit_cast(d2v, __builtin_amdgcn_raw_buffer_load_b128(r, a.lo + off, a.so(k), 0));
   const d2v hi = __builtin_bit_cast(d2v, __builtin_amdgcn_raw_buffer_load_b128(r, a.lo + off + 16u, a.so(k), 0));
-  stale_chk(lo, a, k, off, 0);
-  stale_chk(hi, a, k, off, 1);
   return f4{lo.x, lo.y, hi.x, hi.y};
 }
 __device__ __forceinline__ f2 rld2(Rsrc r, const RA& a, int k, unsigned off) {
   const d2v v = __builtin_bit_cast(d2v, __builtin_amdgcn_raw_buffer_load_b128(r, a.lo + off, a.so(k), 0));
-  stale_chk(v, a, k, off, 2);
   return __builtin_bit_cast(f2, v);
 }
 __device__ __forceinline__ void rst4(Rsrc r, const RA& a, int k, unsigned off, f4 v) {
@@ -347,7 +292,7 @@ __device__ __forceinline__ void rst4(Rsrc r, const RA& a, int k, unsigned off, f
   st128(d2v{v.z, v.w}, r, a.lo + off + 16u, a.so(k));
 }
 __device__ __forceinline__ void rst2(Rsrc r, const RA& a, int k, unsigned off, f2 v) { st128(v, r, a.lo + off, a.so(k)); }
-#elif !defined(DTMPC_FAST_GLOBAL)
+#else
 __device__ __forceinline__ f4 rld4(Rsrc r, const RA& a, int k, unsigned off) {
   return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, a.lo + off, a.so(k), 0));
 }
@@ -356,21 +301,7 @@ __device__ __forceinline__ f2 rld2(Rsrc r, const RA& a, int k, unsigned off) {
 }
 __device__ __forceinline__ void rst4(Rsrc r, const RA& a, int k, unsigned off, f4 v) { st128(v, r, a.lo + off, a.so(k)); }
 __device__ __forceinline__ void rst2(Rsrc r, const RA& a, int k, unsigned off, f2 v) {
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, v), r, a.lo + off, a.so(k), DTMPC_FAST_STPOL);
-}
-#else  // A/B: the same records through global loads / stores with a scalar row base
-__device__ __forceinline__ const char* kargs_ws();
-__device__ __forceinline__ f4 rld4(Rsrc, const RA& a, int k, unsigned off) {
-  return *(const f4*)gaddr(kargs_ws(), (size_t)a.so(k), a.lo + off);
-}
-__device__ __forceinline__ f2 rld2(Rsrc, const RA& a, int k, unsigned off) {
-  return *(const f2*)gaddr(kargs_ws(), (size_t)a.so(k), a.lo + off);
-}
-__device__ __forceinline__ void rst4(Rsrc, const RA& a, int k, unsigned off, f4 v) {
-  *(f4*)gaddr(kargs_ws(), (size_t)a.so(k), a.lo + off) = v;
-}
-__device__ __forceinline__ void rst2(Rsrc, const RA& a, int k, unsigned off, f2 v) {
-  *(f2*)gaddr(kargs_ws(), (size_t)a.so(k), a.lo + off) = v;
+  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, v), r, a.lo + off, a.so(k), 0);
 }
 #endif
 
@@ -433,20 +364,11 @@ __device__ __forceinline__ f2 vclamp(f2 v, real lo, real hi) { return f2{vclamp(
 __device__ __forceinline__ real vmaxnan(real a, real b) { return __builtin_elementwise_maximum(a, b); }
 // a * b + c of the forward passes (dynamics, h_i, DBaS update, costs, the commit's u): one fused
 // rounding (v_fma / v_pk_fma; measured 4.66 -> 4.55 ms), the rounding of the oracle's FMA-contraction
-// build; DTMPC_FAST_FWD_FMA=0 rounds twice, as the reference's separate torch ops do.  Written at the
-// same places of the line search, the commit and the start rollout, so either way a committed tape is
-// the candidate priced.
-#ifndef DTMPC_FAST_FWD_FMA
-#define DTMPC_FAST_FWD_FMA 1
-#endif
+// build (the reference's separate torch ops round twice).  Written at the same places of the line search,
+// the commit and the start rollout, so a committed tape is the candidate priced.
 template <class V>
 __device__ __forceinline__ V ffma(V a, V b, V c) {
-#if DTMPC_FAST_FWD_FMA
   return __builtin_elementwise_fma(a, b, c);
-#else
-  DTMPC_NOCONTRACT
-  return a * b + c;
-#endif
 }
 #if DTMPC_FAST_F64
 // f64: exp / log as the generic f64 kernel evaluates them (OCML), the smooth-min terms as it forms them
@@ -454,13 +376,11 @@ __device__ __forceinline__ V ffma(V a, V b, V c) {
 // fdlibm kernels __kernel_sin / __kernel_cos on [-pi/4, pi/4] (< 1 ulp), the quadrant applied by exact
 // products with (A, B) in {0, +-1} as in the f32 form; |x| > 2^20 and non-finite take OCML sincos, out of
 // line (its Payne-Hanek branch would otherwise be inlined into every rollout step).
-// DTMPC_FAST64_EXP = 1: OCML's exp_f64 operation for operation (the same reduction, coefficients and fma order,
+// exp_sm: OCML's exp_f64 operation for operation (the same reduction, coefficients and fma order,
 // so bitwise the same values on [-1075, 1024]) without its two range selects -- every caller's argument is a
 // smooth-min exponent in [-50, 0] or NaN -- and with the polynomial's fmas in the three-address form
-// (v_fma_f64): the compiler otherwise emits each as a copy of the coefficient plus a two-address v_fmac_f64.
-#ifndef DTMPC_FAST64_EXP
-#define DTMPC_FAST64_EXP 3
-#endif
+// (v_fma_f64): the compiler otherwise emits each as a copy of the coefficient plus a two-address v_fmac_f64
+// (against OCML's exp and the plain-fma form: profiles/r05/ab_f64_exp.txt).
 template <bool ASM>
 __device__ __forceinline__ double exp_sm(double x) {
   const double k = __builtin_rint(x * 0x1.71547652b82fep+0);
@@ -499,44 +419,24 @@ __device__ __forceinline__ double exp_sm(double x) {
   q = __builtin_fma(r, q, 1.0);
   return __builtin_ldexp(q, (int)k);
 }
-#ifdef DTMPC_DIAG_CHEAPEXP  // timing only (wrong results by design): exp through v_exp_f32
-__device__ __forceinline__ real vexp(real x) { return (double)__builtin_amdgcn_exp2f((float)(x * 1.4426950408889634)); }
-#elif DTMPC_FAST64_EXP
 __device__ __forceinline__ real vexp(real x) { return exp_sm<false>(x); }
-#else
-__device__ __forceinline__ real vexp(real x) { return m_exp(x); }
-#endif
 __device__ __forceinline__ f2 vexp(f2 x) { return f2{vexp(x.x), vexp(x.y)}; }
 // 1 / x and a / b for the call sites whose divisor is a finite positive normal or NaN (the barrier's max(z, eps),
-// the smooth-min sum se in [1, M], the log's 2 + f in [1.4, 2.9]).  DTMPC_FAST64_RCP = 1: v_rcp_f64 (~2^-23
+// the smooth-min sum se in [1, M], the log's 2 + f in [1.4, 2.9]): v_rcp_f64 (~2^-23
 // relative) and two Newton steps (1 / x within an ulp); the quotient a r corrected by one residual step, i.e. 5 and
-// 6 instructions against IEEE division's 11 (div_scale, div_fmas, div_fixup).  0: IEEE division.
-#ifndef DTMPC_FAST64_HGLOG
-#define DTMPC_FAST64_HGLOG 1
-#endif
-#ifndef DTMPC_FAST64_RCP
-#define DTMPC_FAST64_RCP 1
-#endif
+// 6 instructions against IEEE division's 11 (div_scale, div_fmas, div_fixup; profiles/r05/ab_f64_exp.txt).
 __device__ __forceinline__ real frcp(real x) {
-#if DTMPC_FAST64_RCP
   double r = __builtin_amdgcn_rcp(x);
   double e = __builtin_fma(-x, r, 1.0);
   r = __builtin_fma(r, e, r);
   e = __builtin_fma(-x, r, 1.0);
   return __builtin_fma(r, e, r);
-#else
-  return 1.0 / x;
-#endif
 }
 __device__ __forceinline__ real fdiv(real a, real b) {
-#if DTMPC_FAST64_RCP
   double r = __builtin_amdgcn_rcp(b);
   r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
   const double q = a * r;
   return __builtin_fma(r, __builtin_fma(-b, q, a), q);
-#else
-  return a / b;
-#endif
 }
 // the smooth-min log log(se), se in [1, M] (its largest term is exp(0)): fdlibm's e_log -- frexp, s = f / (2 + f),
 // a degree-14 odd polynomial in s (< 1 ulp), ~35 instructions against OCML's ~90 (a double-double evaluation);
@@ -572,18 +472,13 @@ __device__ __forceinline__ V smarg(const FP& p, V hi, V zmax) {
   DTMPC_NOCONTRACT
   return p.neg_beta * hi - zmax;
 }
-#if DTMPC_FAST64_EXP
 // branch-free: the caller's wave-uniform branch already decided that some lane needs this term; exp_sm of an
 // argument below -50 (down to -inf) is a finite number, 0 or NaN and is replaced by 0
 template <int M = 0>
 __device__ __forceinline__ real smexp(real x) {
-  const real e = exp_sm<Obs<M>::xasm && DTMPC_FAST64_EXP == 3>(x);
+  const real e = exp_sm<Obs<M>::xasm>(x);
   return x < -kSmSkip ? 0.0 : e;
 }
-#else
-template <int M = 0>
-__device__ __forceinline__ real smexp(real x) { return x < -kSmSkip ? 0.0 : vexp(x); }
-#endif
 template <int M = 0>
 __device__ __forceinline__ f2 smexp(f2 x) { return f2{smexp<M>(x.x), smexp<M>(x.y)}; }
 __device__ __forceinline__ bool smneed(real x) { return !(x < -kSmSkip); }  // NaN: needed (it propagates)
@@ -595,9 +490,6 @@ __device__ __forceinline__ V smterm(const FP& p, V hi, V zmax, V) {
   if (__builtin_amdgcn_ballot_w64(smneed(x))) e = smexp<M>(x);  // wave-uniform
   return e;
 }
-#ifndef DTMPC_FAST_SINCOS_AB
-#define DTMPC_FAST_SINCOS_AB 1
-#endif
 constexpr double kDPio2A = 1.5707963267948966, kDPio2B = 6.123233995736766e-17, kDPio2C = -1.4973849048591698e-33,
                  kD2oPi = 0.6366197723675814;
 constexpr double kDS1 = -1.66666666666666324348e-01, kDS2 = 8.33333333332248946124e-03,
@@ -606,58 +498,24 @@ constexpr double kDS1 = -1.66666666666666324348e-01, kDS2 = 8.333333333322489461
 constexpr double kDC1 = 4.16666666666666019037e-02, kDC2 = -1.38888888888741095749e-03,
                  kDC3 = 2.48015872894767294178e-05, kDC4 = -2.75573143513906633035e-07,
                  kDC5 = 2.08757232129817482790e-09, kDC6 = -1.13596475577881948265e-11;
-// 1: OCML sincos out of line (the default); 0: inline in the cold branch; 2: none (ISA experiments only).
-// Round 3 measured wrong results with 0 on the one-lane f64 kernel (test_tube_step_fast64_vs_generic[1]);
-// on the round-4 source 0 and 1 are bitwise equal over two closed-loop steps (default contraction and
-// -ffp-contract=off alike) and 0 passes that test (profiles/r04/f64_far_sincos.txt).  The two sources differ
-// in the inline form's SGPR spilling (482 -> 403 spills to VGPR lanes in the cold-branch kernel), which is
-// where a compiler defect would sit; the round-3 build is not reproducible, so 1 stays the default.
-#ifndef DTMPC_FAST64_FAR
-#define DTMPC_FAST64_FAR 1
-#endif
-#ifndef DTMPC_FAST64_FARRET
-#define DTMPC_FAST64_FARRET 1
-#endif
+// the far range: OCML sincos out of line.  Inlined into the cold branch it gave wrong results on the round-3
+// one-lane f64 kernel and costs SGPR spills in every caller (profiles/r04/f64_far_sincos.txt, r04/m8_receding.txt).
 struct SinCos {
   double s, c;
 };
-#if DTMPC_FAST64_FARRET
 // returned by value (v0..v3): no out-parameter, so no local of the caller ever has its address taken
-#if DTMPC_FAST64_FAR == 1
 __device__ __attribute__((noinline)) SinCos sincos_far(double x) {
-#else
-__device__ __forceinline__ SinCos sincos_far(double x) {
-#endif
   SinCos r;
   sincos(x, &r.s, &r.c);
   return r;
 }
-#elif DTMPC_FAST64_FAR == 1
-__device__ __attribute__((noinline)) void sincos_far(double x, double* s, double* c) {
-#ifdef DTMPC_FAST_DIAG_FARPRINT
-  printf("DIAG far x=%.17g\n", x);
-#endif
-  sincos(x, s, c);
-#ifdef DTMPC_FAST_DIAG_FARWAIT
-  __builtin_amdgcn_s_waitcnt(0);
-#endif
-}
-#else
-__device__ __forceinline__ void sincos_far(double x, double* s, double* c) { sincos(x, s, c); }
-#endif
 __device__ __forceinline__ void vsincos(real x, real& sn, real& cs) {
-#if DTMPC_FAST64_FAR != 2
   if (__builtin_expect(!(__builtin_fabs(x) <= 1048576.0), 0)) {
-#if DTMPC_FAST64_FARRET
     const SinCos r = sincos_far(x);
     sn = r.s;
     cs = r.c;
-#else
-    sincos_far(x, &sn, &cs);
-#endif
     return;
   }
-#endif
   const double q = __builtin_rint(x * kD2oPi);
   double r = __builtin_fma(-q, kDPio2A, x);
   r = __builtin_fma(-q, kDPio2B, r);
@@ -707,9 +565,6 @@ __device__ __forceinline__ V smterm(const FP& p, V hi, V, V zl) {
 // quadrant-selected ones (the sign of a zero result aside); |x| > 65536 and non-finite take OCML.
 // Same operations element by element in the scalar (commit, start rollout, plant) and the pair (line
 // search) form: a committed tape is bitwise the candidate priced.
-#ifndef DTMPC_FAST_SINCOS_AB
-#define DTMPC_FAST_SINCOS_AB 1
-#endif
 __device__ __forceinline__ void sincos_poly(real r, real& s, real& c) {
   const real z = r * r;
   real ps = __builtin_fmaf(z, kSinS3, kSinS2);
@@ -720,7 +575,6 @@ __device__ __forceinline__ void sincos_poly(real r, real& s, real& c) {
   c = __builtin_fmaf(z * z, pc, __builtin_fmaf(-0.5f, z, 1.0f));
 }
 __device__ __forceinline__ void vsincos(real x, real& sn, real& cs) {
-#if DTMPC_FAST_SINCOS_AB
   if (__builtin_expect(!(__builtin_fabsf(x) <= 65536.0f), 0)) {
     sincosf(x, &sn, &cs);
     return;
@@ -735,9 +589,6 @@ __device__ __forceinline__ void vsincos(real x, real& sn, real& cs) {
   const real A = 1.f - __builtin_fabsf(m), Bq = __builtin_fminf(m, 2.f - m);
   sn = __builtin_fmaf(s, A, c * Bq);
   cs = __builtin_fmaf(c, A, -(s * Bq));
-#else
-  m_sincos(x, &sn, &cs);
-#endif
 }
 __device__ __forceinline__ void vsincos(f2 x, f2& s, f2& c) { pk_sincos(x, s, c); }
 #endif
@@ -819,8 +670,8 @@ template <int M>
 __device__ __forceinline__ real h_grad(const FP& p, real px, real py, real& gx, real& gy) {
 #pragma clang fp contract(off)
   constexpr int MO = Obs<M>::n;
-  // kLds (f64): the per-obstacle values are evaluated again in the sum pass instead of kept (bitwise the same)
-  constexpr bool TWO = Obs<M>::lds;
+  // kReread (f64): the per-obstacle values are evaluated again in the sum pass instead of kept (bitwise the same)
+  constexpr bool TWO = Obs<M>::reread;
   constexpr int MK = TWO ? 1 : MO;
   real z[MK], hh[MK], dxs[MK], dys[MK], zmax = 0.f;
 #pragma unroll
@@ -871,7 +722,7 @@ __device__ __forceinline__ real h_grad(const FP& p, real px, real py, real& gx, 
   gy = sy * inv;
   // untightened also under kTight: the reference linearises the nominal with dubins_augmented_jacobian of
   // the plain h (core/tube_mpc.py:315-320) while its dynamics see h - s (:273-276); dtmpc_solver.hpp alike
-#if DTMPC_FAST_F64 && DTMPC_FAST64_HGLOG
+#if DTMPC_FAST_F64
   return p.neg_inv_beta * (zmax + vlog(se));  // the line search's log (fdlibm, < 1 ulp) instead of OCML's
 #else
   return p.neg_inv_beta * (zmax + m_log(se));
@@ -997,9 +848,6 @@ __device__ __forceinline__ V term(const FCost& c, V x0, V x1, V x2, V b, real r0
 // K_row . e of the feedback du = k + K (x - X_k) (core/ddp.py:267-268), as an fma chain: the
 // reference's K @ dx is a BLAS/ATen matrix-vector product whose summation and fusion are its own; the
 // line search and the commit use this same chain, so a committed tape is the candidate priced.
-#ifndef DTMPC_FAST_KFMA
-#define DTMPC_FAST_KFMA 1
-#endif
 template <bool G0, class V>
 __device__ __forceinline__ V kdot(const f4& K, V e0, V e1, V e2, V e3) {
   V t = K.x * e0;
@@ -1012,7 +860,7 @@ __device__ __forceinline__ V kdot(const f4& K, V e0, V e1, V e2, V e3) {
 // the tapes one iLQR solve works on
 // RROLL (TRACK): the references are an exact rollout of their controls from X_ref[0] by this kernel's own
 // arithmetic -- the tube step's and the general path's ancillary solves, whose references are the nominal solve's
-// tape -- so the f32 line search may re-roll them instead of reading them (LS_RECOMP).  The standalone iLQR takes
+// tape -- so the f32 line search may re-roll them instead of reading them (RC in line_search).  The standalone iLQR takes
 // any caller references (X_ref need not be a rollout of U_ref): RROLL = false, every reference row is read.
 // The sin / cos cache (SCC; f32, one lane per trajectory, gamma = 0 records): sin and cos of the CURRENT tape's heading
 // theta_k, k = 0..N-1, in the workgroup's LDS as sc[k][threadIdx.x] = (sin, cos) -- one ds_write_b64 / ds_read_b64 per
@@ -1194,29 +1042,17 @@ __device__ __forceinline__ real init_tape(const FP& p, const FCost& c, const rea
   return J + term<TRACK, Obs<M>::wrap>(c, s0, s1, s2, sb, R.x, R.y, R.z);
 }
 
-// DTMPC_FAST_RIC_FMA = 1 (round 6): the backward step -- this Jacobian and the Riccati step (riccati_pk) -- compiled
+// The backward step (round 6) -- this Jacobian and the Riccati step (riccati_pk) -- compiled
 // without implicit contraction, its multiply-adds as explicit fmas at fixed places (rfm / fma2): every rounding of the
 // recursion is written in the source, so the lane forms, the record forms and every code placement get the same bits
-// (with implicit contraction the compiler re-rounded it per call site: DESIGN.md section 3 "Four lanes").
-#ifndef DTMPC_FAST_RIC_FMA
-#define DTMPC_FAST_RIC_FMA 1
-#endif
-// a * b + c as one rounding (RIC_FMA) or two
+// (with implicit contraction the compiler re-rounded it per call site: DESIGN.md section 3 "Four lanes";
+// profiles/r06/ab_ric.txt).
+// a * b + c as one rounding
 __device__ __forceinline__ real rfm(real a, real b, real c) {
-#if DTMPC_FAST_RIC_FMA
   return __builtin_elementwise_fma(a, b, c);  // the value type's own fma (__builtin_fma is the double one)
-#else
-  DTMPC_NOCONTRACT
-  return a * b + c;
-#endif
 }
 __device__ __forceinline__ f2 rfm2(f2 a, f2 b, f2 c) {
-#if DTMPC_FAST_RIC_FMA
   return __builtin_elementwise_fma(a, b, c);
-#else
-  DTMPC_NOCONTRACT
-  return a * b + c;
-#endif
 }
 // (a0 b0 + a1 b1 + c) + a3 b3 in the reference's left-to-right order: the P A / S A row sums (and Q_x's) of the step
 __device__ __forceinline__ real rdot3c(real a0, real b0, real a1, real b1, real c, real a3, real b3) {
@@ -1226,9 +1062,7 @@ __device__ __forceinline__ real rdot3c(real a0, real b0, real a1, real b1, real 
 // sparse augmented Jacobian (make_jac, core/systems/dubins_aug_jac.py:61-139)
 __device__ __forceinline__ Jac<real> jac(const FP& p, real sn, real cs, real v, real gxk, real gyk, real dBk,
                                           real gxn, real gyn, real dBn) {
-#if DTMPC_FAST_RIC_FMA
   DTMPC_NOCONTRACT
-#endif
   Jac<real> J;
   const real dt = p.dt;
   J.a02 = -dt * v * sn;
@@ -1238,19 +1072,11 @@ __device__ __forceinline__ Jac<real> jac(const FP& p, real sn, real cs, real v, 
   J.b21 = dt;
   const real r0 = dBn * gxn, r1 = dBn * gyn, r2 = dBn * 0.f;
   const real gd = p.gamma * dBk;
-#if DTMPC_FAST_RIC_FMA
   J.a30 = rfm(-gd, gxk, r0);
   J.a31 = rfm(-gd, gyk, r1);
   J.a32 = (rfm(r1, J.a12, r0 * J.a02) + r2) - gd * 0.f;
   J.g = p.gamma;
   J.b30 = rfm(r1, J.b10, r0 * J.b00);
-#else
-  J.a30 = r0 - gd * gxk;
-  J.a31 = r1 - gd * gyk;
-  J.a32 = (r0 * J.a02 + r1 * J.a12 + r2) - gd * 0.f;
-  J.g = p.gamma;
-  J.b30 = r0 * J.b00 + r1 * J.b10;
-#endif
   J.b31 = r2 * dt;
   return J;
 }
@@ -1262,12 +1088,12 @@ __device__ __forceinline__ Jac<real> jac(const FP& p, real sn, real cs, real v, 
 // same products as riccati_step (the reference's dense update restricted to the nonzeros of A, B),
 // contracted and grouped for pairs: V_xx' = Q_xx + K^T Q_uu K + K^T Q_ux + Q_xu K accumulated term by
 // term in one fma chain per pair.
-#ifndef DTMPC_FAST_RICPK
-#define DTMPC_FAST_RICPK 1
-#endif
 struct RicP {
   f2 V[4][2];  // V_xx: row i, columns (0, 1) and (2, 3)
   f2 Vx[2];    // (V_x0, V_x1), (V_x2, V_x3)
+  __device__ __forceinline__ real vx(int i) const {  // V_x[i]
+    return i == 0 ? Vx[0].x : i == 1 ? Vx[0].y : i == 2 ? Vx[1].x : Vx[1].y;
+  }
 };
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f2 bc(real v) { return f2{v, v}; }
@@ -1281,9 +1107,7 @@ __device__ __forceinline__ f2 bc(real v) { return f2{v, v}; }
 template <bool G0>
 __device__ __forceinline__ bool riccati_pk(const Jac<real>& J, const real* lx, const real* lu, const real* lxx,
                                            const real* luu, real reg, RicP& R, real* K, real* kff) {
-#if DTMPC_FAST_RIC_FMA
   DTMPC_NOCONTRACT  // every rounding of the step is written below (rfm / fma2): the same bits at every call site
-#endif
   const real a02 = J.a02, a12 = J.a12, a30 = J.a30, a31 = J.a31, a32 = J.a32, g = J.g;
   const real b00 = J.b00, b10 = J.b10, b21 = J.b21, b30 = J.b30, b31 = J.b31;
   const f2 A3 = f2{a30, a31};
@@ -1293,17 +1117,10 @@ __device__ __forceinline__ bool riccati_pk(const Jac<real>& J, const real* lx, c
   const f2 V31 = G0 ? f2{0.f, lxx[3]} : R.V[3][1];
   // Q_x = l_x + A^T V_x ; Q_u = l_u + B^T V_x
   const f2 Qx01 = f2{lx[0], lx[1]} + fma2(A3, bc(vx3), R.Vx[0]);
-#if DTMPC_FAST_RIC_FMA
   const real Qx2 = lx[2] + rdot3c(a02, vx0, a12, vx1, vx2, a32, vx3);
   const real Qx3 = G0 ? lx[3] : rfm(g, vx3, lx[3]);
   const real Qu0 = lu[0] + rfm(b30, vx3, rfm(b10, vx1, b00 * vx0));
   const real Qu1 = G0 ? rfm(b21, vx2, lu[1]) : lu[1] + rfm(b31, vx3, b21 * vx2);
-#else
-  const real Qx2 = lx[2] + (a02 * vx0 + a12 * vx1 + vx2 + a32 * vx3);
-  const real Qx3 = G0 ? lx[3] : lx[3] + g * vx3;
-  const real Qu0 = lu[0] + (b00 * vx0 + b10 * vx1 + b30 * vx3);
-  const real Qu1 = G0 ? lu[1] + b21 * vx2 : lu[1] + (b21 * vx2 + b31 * vx3);
-#endif
   // P = A^T V_xx
   f2 P[4][2];
   if (G0) {
@@ -1330,11 +1147,7 @@ __device__ __forceinline__ bool riccati_pk(const Jac<real>& J, const real* lx, c
   for (int i = 0; i < NR; ++i) {
     const real p0 = P[i][0].x, p1 = P[i][0].y, p2 = P[i][1].x, p3 = P[i][1].y;
     Q[i][0] = fma2(A3, bc(p3), P[i][0]);
-#if DTMPC_FAST_RIC_FMA
     Q[i][1] = f2{rdot3c(a02, p0, a12, p1, p2, a32, p3), G0 ? 0.f : g * p3};
-#else
-    Q[i][1] = f2{a02 * p0 + a12 * p1 + p2 + a32 * p3, G0 ? 0.f : g * p3};
-#endif
   }
   Q[0][0].x = lxx[0] + Q[0][0].x;
   Q[1][0].y = lxx[1] + Q[1][0].y;
@@ -1366,20 +1179,13 @@ __device__ __forceinline__ bool riccati_pk(const Jac<real>& J, const real* lx, c
   for (int a = 0; a < 2; ++a) {
     const real s0 = S[a][0].x, s1 = S[a][0].y, s2 = S[a][1].x, s3 = S[a][1].y;
     Qux[a][0] = fma2(A3, bc(s3), S[a][0]);
-#if DTMPC_FAST_RIC_FMA
     Qux[a][1] = f2{rdot3c(a02, s0, a12, s1, s2, a32, s3), G0 ? 0.f : g * s3};
     Quu[a][0] = rfm(s3, b30, rfm(s1, b10, s0 * b00));
     Quu[a][1] = G0 ? s2 * b21 : rfm(s3, b31, s2 * b21);
-#else
-    Qux[a][1] = f2{a02 * s0 + a12 * s1 + s2 + a32 * s3, G0 ? 0.f : g * s3};
-    Quu[a][0] = s0 * b00 + s1 * b10 + s3 * b30;
-    Quu[a][1] = G0 ? s2 * b21 : s2 * b21 + s3 * b31;
-#endif
   }
   Quu[0][0] = luu[0] + Quu[0][0];
   Quu[1][1] = luu[1] + Quu[1][1];
   // gains with the regularised Q_uu (:239-249): LU with partial pivoting, K = -x, k = -x
-#if DTMPC_FAST_RIC_FMA
   // lu2 (dtmpc_device.hpp) with its one multiply-add fused: u11 = a11 - l a01
   LU2<real> f;
   {
@@ -1392,33 +1198,18 @@ __device__ __forceinline__ bool riccati_pk(const Jac<real>& J, const real* lx, c
     f.a00 = a00;
     f.a01 = a01;
   }
-#else
-  const LU2<real> f = lu2(Quu[0][0] + reg, Quu[0][1], Quu[1][0], Quu[1][1] + reg);
-#endif
   f2 Kp[2][2];  // K row a, columns (0, 1) and (2, 3)
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const f2 r0 = Qux[0][c], r1 = Qux[1][c];
     const f2 p0 = f2{f.sw ? r1.x : r0.x, f.sw ? r1.y : r0.y}, p1 = f2{f.sw ? r0.x : r1.x, f.sw ? r0.y : r1.y};
-#if DTMPC_FAST_RIC_FMA
     Kp[1][c] = rfm2(bc(-f.l), p0, p1) * bc(-f.inv11);
     Kp[0][c] = rfm2(bc(f.a01), Kp[1][c], p0) * bc(-f.inv00);
-#else
-    const f2 y1 = p1 - bc(f.l) * p0;
-    Kp[1][c] = y1 * bc(-f.inv11);
-    Kp[0][c] = (p0 + bc(f.a01) * Kp[1][c]) * bc(-f.inv00);
-#endif
   }
   {
     const real p0 = f.sw ? Qu1 : Qu0, p1 = f.sw ? Qu0 : Qu1;
-#if DTMPC_FAST_RIC_FMA
     kff[1] = rfm(-f.l, p0, p1) * -f.inv11;
     kff[0] = rfm(f.a01, kff[1], p0) * -f.inv00;
-#else
-    const real y1 = p1 - f.l * p0;
-    kff[1] = y1 * -f.inv11;
-    kff[0] = (p0 + f.a01 * kff[1]) * -f.inv00;
-#endif
   }
   K[0] = Kp[0][0].x;
   K[1] = Kp[0][0].y;
@@ -1522,16 +1313,11 @@ __device__ __forceinline__ Lin lin_point_sc(const FP& p, const f4& X, f2 sc) {
 // trajectory, and handed to every lane by DPP broadcasts; the Riccati recursion itself is sequential
 // and runs on every lane (each needs the gains).  Same operations on the same values as P = 1: the
 // gains are bitwise those of the one-lane form.
-// DTMPC_FAST_BW_BCAST (DESIGN.md section 3 "Small batches: the four-lane step's latency"): at P > 1 the step inputs
-// come from the group's per-lane rows by DPP instead of being loaded one step ahead -- 2 (default since round 6): in the
-// step itself, lane j of the group owning row k; 1: handed on one step ahead.  The same values; round 5 left both off
-// because the compiler contracted the Riccati step differently in each form.  Since round 6 the step's rounding is
-// written in the source (DTMPC_FAST_RIC_FMA), so every form gives the same bits (tests/test_gpu_lanes.py) and the
-// in-step form is taken for its latency: B = 4,096 tube step 1.94 -> 1.85 ms, config-2 DDP 0.656 -> 0.630 ms,
-// f64 B = 8,192 4.65 -> 4.29 ms (profiles/r06/ab_ric.txt).
-#ifndef DTMPC_FAST_BW_BCAST
-#define DTMPC_FAST_BW_BCAST 2
-#endif
+// At P > 1 the step inputs too come from the group's per-lane rows by DPP, in the step itself (lane j of the group owns
+// row k), instead of being loaded one step ahead (DESIGN.md section 3 "Small batches: the four-lane step's latency").
+// The step's rounding is written in the source, so this gives the bits of the load form (tests/test_gpu_lanes.py); it
+// is taken for its latency: B = 4,096 tube step 1.94 -> 1.85 ms, config-2 DDP 0.656 -> 0.630 ms, f64 B = 8,192
+// 4.65 -> 4.29 ms (profiles/r06/ab_ric.txt).
 template <bool TRACK, int M, class SV>
 __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, const SV& S, int h) {
   constexpr int P = SV::lanes;
@@ -1553,7 +1339,6 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
     // WRAP: phi_x against the wrapped target x - wrap(x - t) (run_nominal.py:318-324, deriv_dx)
     d2 = Obs<M>::wrap ? xn2 - (xn2 - vwrap(xn2 - c.tg.z)) : xn2 - c.tg.z;
   }
-#if DTMPC_FAST_RICPK
   RicP R;
   R.V[0][0] = f2{pxx[0], 0.f};
   R.V[0][1] = f2{0.f, 0.f};
@@ -1565,25 +1350,11 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
   R.V[3][1] = f2{0.f, pxx[3]};
   R.Vx[0] = f2{pxx[0] * d0, pxx[1] * d1};
   R.Vx[1] = f2{pxx[2] * d2, pxx[3] * xnb};
-#define RVX(i) ((i) == 0 ? R.Vx[0].x : (i) == 1 ? R.Vx[0].y : (i) == 2 ? R.Vx[1].x : R.Vx[1].y)
-#else
-  Riccati<real> R;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) R.Vxx[i][j] = i == j ? pxx[i] : 0.f;
-  R.Vx[0] = pxx[0] * d0;
-  R.Vx[1] = pxx[1] * d1;
-  R.Vx[2] = pxx[2] * d2;
-  R.Vx[3] = pxx[3] * xnb;
-#define RVX(i) (R.Vx[i])
-#endif
   real gxn, gyn;
   real dBn = dbarrier(p, h_grad<M>(p, xn0, xn1, gxn, gyn));
-  bool ok = finite(RVX(0)) && finite(RVX(1)) && finite(RVX(2)) && finite(RVX(3));
-  // step inputs one step ahead (P > 1 with BW_BCAST 1: after the first, from the group's per-lane rows; 2: none, every
-  // step takes its inputs from the group's rows by broadcast)
-  constexpr bool BCI = P > 1 && DTMPC_FAST_BW_BCAST == 2;
+  bool ok = finite(R.vx(0)) && finite(R.vx(1)) && finite(R.vx(2)) && finite(R.vx(3));
+  // step inputs one step ahead (P > 1: none, every step takes its inputs from the group's rows by broadcast)
+  constexpr bool BCI = P > 1;
   f4 nX = BCI ? f4{0.f, 0.f, 0.f, 0.f} : S.x(N - 1), nR = f4{0.f, 0.f, 0.f, 0.f};
   f2 nV = BCI ? f2{0.f, 0.f} : S.u(N - 1), nQ = f2{0.f, 0.f};
   if (TRACK && !BCI) {
@@ -1612,38 +1383,7 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
       lu[1] = luu[1] * u1;
     }
     real Kk[8], kk[2];
-#if DTMPC_FAST_RICPK
     ok = riccati_pk<SV::ric0>(J, lx, lu, lxx, luu, reg, R, Kk, kk) && ok;
-#else
-    ok = riccati_step(J, lx, lu, lxx, luu, reg, R, Kk, kk) && ok;
-#endif
-#ifdef DTMPC_FAST_DIAG_LANES
-    // diagnostics builds: the lanes of a trajectory must hold the same gains (they store the same record)
-    if (P > 1) {
-      int bad = -1;
-      real mine = 0, ref = 0;
-#pragma unroll
-      for (int j = 0; j < 10; ++j) {
-        const real v = j < 8 ? Kk[j] : kk[j - 8];
-        const real r0 = gbc<P, 0>(v);
-        if (__builtin_bit_cast(unsigned long long, (double)v) != __builtin_bit_cast(unsigned long long, (double)r0)) {
-          bad = j;
-          mine = v;
-          ref = r0;
-        }
-      }
-      const real in[9] = {X.x, X.y, X.z, X.w, V.x, V.y, Lk.sn, Lk.gx, Lk.dB};
-      int badin = -1;
-#pragma unroll
-      for (int j = 0; j < 9; ++j)
-        if (__builtin_bit_cast(unsigned long long, (double)in[j]) !=
-            __builtin_bit_cast(unsigned long long, (double)gbc<P, 0>(in[j])))
-          badin = j;
-      if (bad >= 0 || badin >= 0)
-        printf("DIAG lanes blk=%d thr=%d h=%d k=%d gain=%d mine=%.17g lane0=%.17g input=%d\n", (int)blockIdx.x,
-               (int)threadIdx.x, h, k, bad, (double)mine, (double)ref, badin);
-    }
-#endif
     S.G.template store<SV::g0>(S.r, k, Kk, kk);
     gxn = Lk.gx;
     gyn = Lk.gy;
@@ -1677,7 +1417,7 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
       const int r = kt - h > 0 ? kt - h : 0;
       return rld4(S.r, S.XA, uidx(rb), (unsigned)(r - rb) * S.XA.rs);
     };
-    // BW_BCAST: the step inputs too -- lane h reads the controls (and the ancillary's reference rows) of row kt - h
+    // the step inputs too -- lane h reads the controls (and the ancillary's reference rows) of row kt - h
     // one group ahead, and every step takes row k's values from lane kt - k by the same DPP broadcasts instead of
     // reading them one step ahead (a group of P steps of load latency covered instead of one)
     auto prow2 = [&](const RA& A, int kt) {
@@ -1690,27 +1430,21 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
       const int r = kt - h > 0 ? kt - h : 0;
       return rld4(S.r, A, uidx(rb), (unsigned)(r - rb) * A.rs);
     };
-    constexpr bool BC = DTMPC_FAST_BW_BCAST != 0;
     f4 PX = prow(N - 1), PR = f4{0.f, 0.f, 0.f, 0.f};
-    f2 PV = f2{0.f, 0.f}, PQ = f2{0.f, 0.f};
-    if (BC) {
-      PV = prow2(S.UA, N - 1);
-      if (TRACK) {
-        PR = prow4(S.XRA, N - 1);
-        PQ = prow2(S.URA, N - 1);
-      }
+    f2 PV = prow2(S.UA, N - 1), PQ = f2{0.f, 0.f};
+    if (TRACK) {
+      PR = prow4(S.XRA, N - 1);
+      PQ = prow2(S.URA, N - 1);
     }
     for (int kt = N - 1; kt >= 0; kt -= P) {
       const f4 PXc = PX, PRc = PR;
       const f2 PVc = PV, PQc = PQ;
       if (kt - P >= 0) {
         PX = prow(kt - P);
-        if (BC) {
-          PV = prow2(S.UA, kt - P);
-          if (TRACK) {
-            PR = prow4(S.XRA, kt - P);
-            PQ = prow2(S.URA, kt - P);
-          }
+        PV = prow2(S.UA, kt - P);
+        if (TRACK) {
+          PR = prow4(S.XRA, kt - P);
+          PQ = prow2(S.URA, kt - P);
         }
       }
       const Lin Lh = lin_point<M>(p, PXc);
@@ -1718,33 +1452,14 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
       for (int j = 0; j < P; ++j) {
         const int k = kt - j;
         if (k < 0) break;
-        f4 X = nX, Rr = nR;
-        f2 V = nV, Q = nQ;
-        if (BCI) {
-          // BW_BCAST 2 (in-step): step k's inputs from lane j of this group (row kt - j = k), broadcast in the step
-          X = f4{gbcast<P>(PXc.x, j), gbcast<P>(PXc.y, j), gbcast<P>(PXc.z, j), gbcast<P>(PXc.w, j)};
-          V = f2{gbcast<P>(PVc.x, j), gbcast<P>(PVc.y, j)};
-          if (TRACK) {
-            Rr = f4{gbcast<P>(PRc.x, j), gbcast<P>(PRc.y, j), gbcast<P>(PRc.z, j), 0.f};
-            Q = f2{gbcast<P>(PQc.x, j), gbcast<P>(PQc.y, j)};
-          }
-        } else if (BC) {
-          // the inputs of step k - 1, handed on to the next step as next_inputs hands on its loads (the step
-          // itself then reads loop-carried values in both forms): row k - 1 from lane j + 1 of this group, or from
-          // lane 0 of the next group's rows
-          if (k > 0) {
-            const int jn = j + 1 < P ? j + 1 : 0;
-            const f4 XS = j + 1 < P ? PXc : PX, RS = j + 1 < P ? PRc : PR;
-            const f2 VS = j + 1 < P ? PVc : PV, QS = j + 1 < P ? PQc : PQ;
-            nX = f4{gbcast<P>(XS.x, jn), gbcast<P>(XS.y, jn), gbcast<P>(XS.z, jn), gbcast<P>(XS.w, jn)};
-            nV = f2{gbcast<P>(VS.x, jn), gbcast<P>(VS.y, jn)};
-            if (TRACK) {
-              nR = f4{gbcast<P>(RS.x, jn), gbcast<P>(RS.y, jn), gbcast<P>(RS.z, jn), 0.f};
-              nQ = f2{gbcast<P>(QS.x, jn), gbcast<P>(QS.y, jn)};
-            }
-          }
-        } else {
-          next_inputs(k);
+        // step k's inputs from lane j of this group (row kt - j = k), broadcast in the step
+        const f4 X = f4{gbcast<P>(PXc.x, j), gbcast<P>(PXc.y, j), gbcast<P>(PXc.z, j), gbcast<P>(PXc.w, j)};
+        const f2 V = f2{gbcast<P>(PVc.x, j), gbcast<P>(PVc.y, j)};
+        f4 Rr = nR;
+        f2 Q = nQ;
+        if (TRACK) {
+          Rr = f4{gbcast<P>(PRc.x, j), gbcast<P>(PRc.y, j), gbcast<P>(PRc.z, j), 0.f};
+          Q = f2{gbcast<P>(PQc.x, j), gbcast<P>(PQc.y, j)};
         }
         Lin Lk;
         Lk.sn = gbcast<P>(Lh.sn, j);
@@ -1757,8 +1472,7 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
     }
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) ok = ok && finite(RVX(i));
-#undef RVX
+  for (int i = 0; i < 4; ++i) ok = ok && finite(R.vx(i));
   return ok;
 }
 
@@ -1769,29 +1483,16 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
 // pairs, so the instruction stream interleaves NPR independent chains: no dependent pair of packed
 // ops / compare-select sits back to back (each such pair costs an s_nop wait state on gfx950).
 // Arithmetic per candidate is the scalar forward pass (fhat, stage) operation for operation.
-#ifndef DTMPC_FAST_LS_DEPTH2
 // two steps of prefetch lead (f32, one lane per trajectory: measured -1.5 %).  f64: one -- the four step
 // buffers of 21 doubles would not fit beside the candidates (at one lane: 380 scratch spill / reload
 // instructions in the kernel, 23 with two buffers)
-#define DTMPC_FAST_LS_DEPTH2 (DTMPC_FAST_F64 ? 0 : 1)
-#endif
-#ifndef DTMPC_FAST_LS_RECOMP
-// 1 (default): the line search re-rolls the tape's states (and the ancillary's reference states) from their
-// controls at gamma = 0 in f32 instead of reading them: -16 (nominal) / -32 (ancillary) B of reads per step,
-// bitwise the same tapes; same-box A/B (profiles/r04/ab_recompute.txt) time +-0, HBM traffic -15 %
-#define DTMPC_FAST_LS_RECOMP 1
-#endif
-#ifndef DTMPC_FAST64_RECOMP
-// f64: the same re-roll in the f64 line search and commit (the f64 step reads 43.1 GB per launch
-// against 35.96 GB algorithmic because its passes read the tape states the f32 kernel re-rolls)
-#define DTMPC_FAST64_RECOMP 0
-#endif
+constexpr bool kLsDepth2 = !DTMPC_FAST_F64;
 template <int NPR>
 struct Cand {
   f2 a0[NPR], a1[NPR], a2[NPR], ab[NPR], Bp[NPR], J[NPR], al[NPR];
 };
 
-#if !DTMPC_FAST_F64 && !defined(DTMPC_OCML_SINCOS)
+#if !DTMPC_FAST_F64
 // sin / cos of NPR pairs whose elements are all in [-65536, 65536] (no range test, no branch)
 template <int NPR>
 __device__ __forceinline__ void sincos_pairs_fast(const f2* x, f2* sn, f2* cs) {
@@ -1815,7 +1516,6 @@ __device__ __forceinline__ void sincos_pairs_fast(const f2* x, f2* sn, f2* cs) {
       s[q] = __builtin_elementwise_fma(r[q] * z[q], ps, r[q]);
       c[q] = __builtin_elementwise_fma(z[q] * z[q], pc, __builtin_elementwise_fma(f2(-0.5f), z[q], f2(1.0f)));
     }
-#if DTMPC_FAST_SINCOS_AB
     f2 A[NPR], Bq[NPR];
 #pragma unroll
     for (int q = 0; q < NPR; ++q) {
@@ -1830,16 +1530,6 @@ __device__ __forceinline__ void sincos_pairs_fast(const f2* x, f2* sn, f2* cs) {
       sn[q] = __builtin_elementwise_fma(s[q], A[q], c[q] * Bq[q]);
       cs[q] = __builtin_elementwise_fma(c[q], A[q], -(s[q] * Bq[q]));
     }
-#else
-#pragma unroll
-    for (int q = 0; q < NPR; ++q) {
-      const int j0 = (int)qq[q].x & 3, j1 = (int)qq[q].y & 3;
-      const real so0 = (j0 & 1) ? c[q].x : s[q].x, co0 = (j0 & 1) ? s[q].x : c[q].x;
-      const real so1 = (j1 & 1) ? c[q].y : s[q].y, co1 = (j1 & 1) ? s[q].y : c[q].y;
-      sn[q] = f2{(j0 & 2) ? -so0 : so0, (j1 & 2) ? -so1 : so1};
-      cs[q] = f2{((j0 + 1) & 2) ? -co0 : co0, ((j1 + 1) & 2) ? -co1 : co1};
-    }
-#endif
 }
 #endif
 // sin / cos of NPR pairs (pk_sincos per pair); one range test for all of them
@@ -1853,12 +1543,10 @@ __device__ __forceinline__ void sincos_pairs(const f2* x, f2* sn, f2* cs) {
   real m = __builtin_fabsf(x[0].x);
 #pragma unroll
   for (int q = 0; q < NPR; ++q) m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(x[q].x), __builtin_fabsf(x[q].y)));
-#ifndef DTMPC_OCML_SINCOS
   if (__builtin_expect(m <= 65536.0f, 1)) {
     sincos_pairs_fast<NPR>(x, sn, cs);
     return;
   }
-#endif
 #pragma unroll
   for (int q = 0; q < NPR; ++q) {  // some element out of range: each element as the scalar form
     real s0, c0, s1, c1;
@@ -1874,11 +1562,11 @@ __device__ __forceinline__ void sincos_pairs(const f2* x, f2* sn, f2* cs) {
 template <int M, int NPR>
 __device__ __forceinline__ void ls_bar(const FP& p, const f2* px, const f2* py, f2* Bn) {
   DTMPC_NOCONTRACT
-  // smooth-min h over the M obstacles (h_sm), all pairs together.  TWO (kLds, f64): the h_i are not kept between
+  // smooth-min h over the M obstacles (h_sm), all pairs together.  TWO (kReread, f64): the h_i are not kept between
   // the min and the exp pass but evaluated again (the same operations, so bitwise the same values) -- at M = 8
   // the kept 8 x NPR pairs of doubles were what made the general-record kernels spill (build.py check_resources)
   constexpr int MO = Obs<M>::n;
-  constexpr bool TWO = Obs<M>::lds;
+  constexpr bool TWO = Obs<M>::reread;
   f2 hi[TWO ? 1 : MO][NPR], hm[NPR];
   auto hval = [&](int i, int q) {
     const f2 dx = px[q] - ocx<M>(p, i);
@@ -1888,7 +1576,7 @@ __device__ __forceinline__ void ls_bar(const FP& p, const f2* px, const f2* py, 
   (void)hval;  // f32 keeps the h_i (only the f64 exp pass below evaluates them again)
 #pragma unroll
   for (int i = 0; i < MO; ++i) {
-    const real cxi = ocx<M>(p, i), cyi = ocy<M>(p, i), r2i = or2<M>(p, i);  // one read per obstacle (kLds)
+    const real cxi = ocx<M>(p, i), cyi = ocy<M>(p, i), r2i = or2<M>(p, i);  // one read per obstacle (kReread)
 #pragma unroll
     for (int q = 0; q < NPR; ++q) {
       const f2 dx = px[q] - cxi;
@@ -1958,13 +1646,8 @@ __device__ __forceinline__ void ls_step(const FP& p, const FCost& c, const StepI
 #pragma unroll
   for (int q = 0; q < NPR; ++q) {
     const f2 e0 = C.a0[q] - s.X0, e1 = C.a1[q] - s.X1, e2 = C.a2[q] - s.X2, e3 = C.ab[q] - s.X3;
-#if DTMPC_FAST_KFMA
     const f2 du0 = s.kk.x + kdot<G0>(s.Ka, e0, e1, e2, e3);
     const f2 du1 = s.kk.y + kdot<G0>(s.Kb, e0, e1, e2, e3);
-#else
-    const f2 du0 = s.kk.x + (s.Ka.x * e0 + s.Ka.y * e1 + s.Ka.z * e2 + s.Ka.w * e3);
-    const f2 du1 = s.kk.y + (s.Kb.x * e0 + s.Kb.y * e1 + s.Kb.z * e2 + s.Kb.w * e3);
-#endif
     u0[q] = ffma(C.al[q], du0, f2(s.V0));
     u1[q] = ffma(C.al[q], du1, f2(s.V1));
   }
@@ -1999,72 +1682,9 @@ __device__ __forceinline__ void ls_step(const FP& p, const FCost& c, const StepI
   }
 }
 
-// The same step software-pipelined (f32, gamma = 0, four lanes: one candidate pair per lane, i.e. one dependent
-// chain per step).  At gamma = 0 the controls do not read b (K's b column is zero), so b_k = B(h(x_k)) -- which
-// ls_step evaluates at the end of step k - 1, right after the move that produced x_k -- is evaluated here, in
-// step k, beside the move x_k -> x_{k+1}: two independent chains in one basic block, so the smooth-min's exp /
-// log / rcp latencies fill the move's sin / cos chain.  The out-of-range sin / cos case is redone after them
-// (one uniform branch).  Step 0 takes b_0 from the start state (`first`).  The same operations on the same
-// values as ls_step: bitwise the same candidates.  x_k comes back in xk* for the slot stores (row k = x_k, b_k).
-#ifndef DTMPC_FAST_LS_PIPE
-#define DTMPC_FAST_LS_PIPE 0  // A/B: bitwise the same tapes, same time (B = 4,096: 1.91 ms both ways), so off
-#endif
-#if !DTMPC_FAST_F64 && !defined(DTMPC_OCML_SINCOS)
-template <bool TRACK, int M, int NPR>
-__device__ __forceinline__ void ls_step_pipe(const FP& p, const FCost& c, const StepIn& s, Cand<NPR>& C, f2* u0,
-                                             f2* u1, f2* xk0, f2* xk1, f2* xk2, bool first) {
-  DTMPC_NOCONTRACT
-  static_assert(DTMPC_FAST_KFMA, "the pipelined step is written for the fma feedback");
-#pragma unroll
-  for (int q = 0; q < NPR; ++q) {
-    xk0[q] = C.a0[q];
-    xk1[q] = C.a1[q];
-    xk2[q] = C.a2[q];
-    const f2 e0 = C.a0[q] - s.X0, e1 = C.a1[q] - s.X1, e2 = C.a2[q] - s.X2;
-    const f2 du0 = s.kk.x + kdot<true>(s.Ka, e0, e1, e2, e2);
-    const f2 du1 = s.kk.y + kdot<true>(s.Kb, e0, e1, e2, e2);
-    u0[q] = ffma(C.al[q], du0, f2(s.V0));
-    u1[q] = ffma(C.al[q], du1, f2(s.V1));
-  }
-#pragma unroll
-  for (int q = 0; q < NPR; ++q) {
-    u0[q] = vclamp(u0[q], p.umin0, p.umax0);
-    u1[q] = vclamp(u1[q], p.umin1, p.umax1);
-  }
-  real m = __builtin_fabsf(xk2[0].x);
-#pragma unroll
-  for (int q = 0; q < NPR; ++q) m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(xk2[q].x), __builtin_fabsf(xk2[q].y)));
-  f2 sn[NPR], cs[NPR];
-  sincos_pairs_fast<NPR>(xk2, sn, cs);
-  auto move = [&]() {
-#pragma unroll
-    for (int q = 0; q < NPR; ++q) {
-      const f2 dv = p.dt * u0[q];
-      C.a0[q] = ffma(dv, cs[q], xk0[q]);
-      C.a1[q] = ffma(dv, sn[q], xk1[q]);
-      C.a2[q] = ffma(f2(p.dt), u1[q], xk2[q]);
-    }
-  };
-  move();
-  f2 Bn[NPR];
-  ls_bar<M, NPR>(p, xk0, xk1, Bn);
-#pragma unroll
-  for (int q = 0; q < NPR; ++q) {
-    const f2 bk = first ? C.ab[q] : Bn[q];
-    C.J[q] = C.J[q] + stage<TRACK, Obs<M>::wrap>(c, xk0[q], xk1[q], xk2[q], bk, u0[q], u1[q], s.r0, s.r1, s.r2,
-                                                  s.q0, s.q1);
-    C.ab[q] = bk;
-  }
-  if (__builtin_expect(!(m <= 65536.0f), 0)) {
-    sincos_pairs<NPR>(xk2, sn, cs);
-    move();
-  }
-}
-#endif
-
-#ifndef DTMPC_FAST_LS_LEAD4
-#define DTMPC_FAST_LS_LEAD4 4  // P = 4: step inputs in a ring of LEAD + 1 buffers refilled LEAD steps ahead (0: two buffers, as P = 1; B = 4,096: 2.13 ms at 0, 2.03 at 3, 2.01 at 4)
-#endif
+// P = 4: the step inputs in a ring of kLsLead4 + 1 buffers, each refilled kLsLead4 steps ahead (B = 4,096: 2.13 ms with
+// two buffers as P = 1, 2.03 at a lead of 3, 2.01 at 4; profiles/r04/lead_b4096.txt)
+constexpr int kLsLead4 = 4;
 // P = 4: the candidate tapes.  Every lane writes the rollouts of its two candidates into their own
 // slots of the solve's tape records (instead of the winner being re-rolled by a commit pass): slot
 // bank * 6 + candidate, in the bank the current tape is not in; the winner's slot then becomes the
@@ -2117,12 +1737,7 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
     else
       C.al[q] = f2{pick3(hc, cf.cal[0], cf.cal[2], cf.cal[4]), pick3(hc, cf.cal[1], cf.cal[3], cf.cal[5])};
   }
-#if !DTMPC_FAST_F64 && !defined(DTMPC_OCML_SINCOS)
-  constexpr bool PIPE = DTMPC_FAST_LS_PIPE && SV::g0 && P == 4 && DTMPC_FAST_LS_LEAD4 > 0;
-#else
-  constexpr bool PIPE = false;
-#endif
-  if (P == 4 && !PIPE) {  // the candidates' row 0 (PIPE: stored by the first step, row k = (x_k, b_k))
+  if (P == 4) {  // the candidates' row 0
     const f4 X0v = f4{x0[0], x0[1], x0[2], x0[3]};
     rst4(S.r, Z.X0, 0, 0, X0v);
     rst4(S.r, Z.X1, 0, 0, X0v);
@@ -2138,8 +1753,8 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
   };
   f2 u0[NPR], u1[NPR];
   const int N1 = N - 1;
-  if (P == 4 && DTMPC_FAST_LS_LEAD4 > 0) {
-    constexpr int LEAD = DTMPC_FAST_LS_LEAD4 > 0 ? DTMPC_FAST_LS_LEAD4 : 1, R = LEAD + 1;
+  if (P == 4) {
+    constexpr int LEAD = kLsLead4, R = LEAD + 1;
     auto ix = [&](int j) { return uidx(j < N1 ? j : N1); };
     StepIn Bf[R];
 #pragma unroll
@@ -2149,37 +1764,17 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
       for (int j = 0; j < R; ++j) {
         load_step<TRACK>(Bf[(j + LEAD) % R], S, ix(k + j + LEAD));
         if (k + j >= N) break;
-#if !DTMPC_FAST_F64 && !defined(DTMPC_OCML_SINCOS)
-        if (PIPE) {
-          f2 xk0[NPR], xk1[NPR], xk2[NPR];
-          ls_step_pipe<TRACK, M, NPR>(p, c, Bf[j], C, u0, u1, xk0, xk1, xk2, k + j == 0);
-          rst2(S.r, Z.U0, k + j, 0, f2{u0[0].x, u1[0].x});
-          rst2(S.r, Z.U1, k + j, 0, f2{u0[0].y, u1[0].y});
-          rst4(S.r, Z.X0, k + j, 0, f4{xk0[0].x, xk1[0].x, xk2[0].x, C.ab[0].x});
-          rst4(S.r, Z.X1, k + j, 0, f4{xk0[0].y, xk1[0].y, xk2[0].y, C.ab[0].y});
-          continue;
-        }
-#endif
         ls_step<TRACK, M, NPR, SV::g0>(p, c, Bf[j], C, u0, u1);
         keep(k + j, u0, u1);
       }
     }
-#if !DTMPC_FAST_F64 && !defined(DTMPC_OCML_SINCOS)
-    if (PIPE) {  // b_N of the final states (the terminal cost's) and the slots' row N
-      f2 Bn[NPR];
-      ls_bar<M, NPR>(p, C.a0, C.a1, Bn);
-#pragma unroll
-      for (int q = 0; q < NPR; ++q) C.ab[q] = Bn[q];
-      rst4(S.r, Z.X0, N, 0, f4{C.a0[0].x, C.a1[0].x, C.a2[0].x, C.ab[0].x});
-      rst4(S.r, Z.X1, N, 0, f4{C.a0[0].y, C.a1[0].y, C.a2[0].y, C.ab[0].y});
-    }
-#endif
   } else {
-  // RC (gamma = 0; f32, and f64 with DTMPC_FAST64_RECOMP): the current tape's states X_k -- and the ancillary's
+  // RC (gamma = 0, f32): the current tape's states X_k -- and the ancillary's
   // reference states -- are not read but re-rolled from their controls by the same Dubins arithmetic that produced
   // them (init_tape / commit / the nominal's solve: rollout(x0, U)), so they are bit for bit the stored rows; their
-  // b is never needed (K's b column is zero at gamma = 0)
-  constexpr bool RC = DTMPC_FAST_LS_RECOMP && SV::g0 && (!DTMPC_FAST_F64 || DTMPC_FAST64_RECOMP);
+  // b is never needed (K's b column is zero at gamma = 0).  -16 (nominal) / -32 (ancillary) B of reads per step, time
+  // +-0, HBM traffic -15 % (profiles/r04/ab_recompute.txt)
+  constexpr bool RC = SV::g0 && !DTMPC_FAST_F64;
   constexpr bool RCR = RC && SV::rroll;  // the references re-rolled too (only when they are a device rollout)
   static_assert(!SV::scc || RC, "the sin / cos cache serves the line search's re-roll of the old tape");
   real o0 = x0[0], o1 = x0[1], o2 = x0[2], q0 = 0.f, q1 = 0.f, q2 = 0.f;
@@ -2208,7 +1803,7 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
       }
     }
   };
-  if (DTMPC_FAST_LS_DEPTH2) {
+  if (kLsDepth2) {
   // four buffers in rotation, each refilled two steps before use
   auto ix = [&](int j) { return uidx(j < N1 ? j : N1); };
   StepIn A, Bs, Cs, Ds;
@@ -2352,15 +1947,7 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
   return ok ? best : -1;
 }
 
-#ifndef DTMPC_FAST_CM_DEPTH2
-#define DTMPC_FAST_CM_DEPTH2 1  // 0: one step of prefetch lead (measured 3 % slower)
-#endif
-#ifndef DTMPC_FAST_CM_LEAD
-#define DTMPC_FAST_CM_LEAD 2
-#endif
-#ifndef DTMPC_FAST_CM_RECOMP
-#define DTMPC_FAST_CM_RECOMP 1  // 1: the old tape's states are re-rolled from its controls, not read (CMR below)
-#endif
+constexpr int kCmLead = 2;  // the commit's prefetch lead in steps (below)
 // materialise the chosen candidate in place (commit_candidate): same arithmetic as its lane of the
 // line search; the old X[k+1] is read (prefetched) before it is overwritten
 template <bool TRACK, int M, class SV>
@@ -2372,7 +1959,7 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
   // re-rolling the old controls by its Dubins part reproduces the old x, y, theta bit for bit (b is never
   // used: K's b column is zero) and saves 16 B per step of HBM reads.  (With gamma != 0 the re-roll would need
   // the barrier too, measured slower in round 2; f64 is instruction-bound: both read the old states.)
-  constexpr bool CMR = DTMPC_FAST_CM_RECOMP && SV::g0 && (!DTMPC_FAST_F64 || DTMPC_FAST64_RECOMP);
+  constexpr bool CMR = SV::g0 && !DTMPC_FAST_F64;
   static_assert(!SV::scc || CMR, "the sin / cos cache serves the commit's re-roll of the old tape");
   real o0 = s0, o1 = s1, o2 = s2;
   constexpr bool LX = !CMR;
@@ -2392,19 +1979,10 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
         dubins(p, o0, o1, o2, cur.V0, cur.V1);
       }
     }
-#if DTMPC_FAST_KFMA
     const real du0 = cur.kk.x + kdot<SV::g0>(cur.Ka, e0, e1, e2, e3);
     const real du1 = cur.kk.y + kdot<SV::g0>(cur.Kb, e0, e1, e2, e3);
-#else
-    const real du0 = cur.kk.x + (cur.Ka.x * e0 + cur.Ka.y * e1 + cur.Ka.z * e2 + cur.Ka.w * e3);
-    const real du1 = cur.kk.y + (cur.Kb.x * e0 + cur.Kb.y * e1 + cur.Kb.z * e2 + cur.Kb.w * e3);
-#endif
     const real u0 = vclamp(ffma(al, du0, cur.V0), p.umin0, p.umax0);
     const real u1 = vclamp(ffma(al, du1, cur.V1), p.umin1, p.umax1);
-#ifdef DTMPC_FAST_DIAG_NOSTORE  // timing attribution only: the commit computes but stores nothing
-    fhat<M>(p, s0, s1, s2, sb, u0, u1, Bc);
-    if (__builtin_isnan(s0 + u0 + u1)) S.stx(k + 1, f4{s0, s1, s2, sb});
-#else
     S.stu(k, f2{u0, u1});
     if constexpr (SV::scc) {
       real sn, cs;
@@ -2414,16 +1992,15 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
       fhat<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc);
     }
     S.stx(k + 1, f4{s0, s1, s2, sb});
-#endif
   };
-#if DTMPC_FAST_CM_DEPTH2
   // R = LEAD + 1 step buffers in rotation: each refilled LEAD steps before it is used (the commit's step
-  // is short, ~190 instructions, and a loaded chip stretches an HBM read past one or two of them).
+  // is short, ~190 instructions, and a loaded chip stretches an HBM read past one or two of them; one step
+  // of lead measured 3 % slower).
   // A refill of step j reads the OLD X[j] before step j-1 overwrites it (issued earlier in program
   // order).  The loop is entered with the same outstanding vector-memory operations as its back edge
   // carries (a refill and two stores per step): X row 0 is rewritten with x0 -- the value it holds --
   // twice after each preload, so the wait-count state at the loop header is the same on both paths.
-  constexpr int LEAD = DTMPC_FAST_CM_LEAD, R = LEAD + 1;
+  constexpr int LEAD = kCmLead, R = LEAD + 1;
   const int N1 = N - 1;
   auto ix = [&](int j) { return uidx(j < N1 ? j : N1); };
   const f4 X0v = f4{x0[0], x0[1], x0[2], x0[3]};
@@ -2442,15 +2019,6 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
       step(Bf[j], k + j);
     }
   }
-#else
-  StepIn cur, nxt;
-  load_step<false, LX>(nxt, T0, 0);
-  for (int k = 0; k < N; ++k) {
-    cur = nxt;
-    if (k + 1 < N) load_step<false, LX>(nxt, T0, k + 1);
-    step(cur, k);
-  }
-#endif
 }
 
 #ifdef DTMPC_PROFILE
@@ -2475,43 +2043,6 @@ __device__ __forceinline__ void ls_stat(int trk, int best, real al, const FIlqr&
     if (__ballot(z || f) == act) atomicAdd(g + 11, 1ull);
   }
 }
-#endif
-
-#ifdef DTMPC_FAST_DIAG
-// diagnostics builds (scripts/diag_f64.sh, not the product): every kernel's kernarg segment starts with its FP, so
-// the problem constants the solver holds in registers (the pinned obstacle table, the scalars) can be compared
-// with the segment's copy at every phase boundary; the first lanes that disagree, or whose solve goes
-// non-finite, print where.  The general path forms its DBaS constants on the device, so only the table and the
-// dynamics constants are compared there.
-template <int MM>
-__device__ __forceinline__ void diag_p(const FP& p, int where, int it) {
-  const FP* q = (const FP*)__builtin_amdgcn_kernarg_segment_ptr();
-  int bad = -1;
-  real v = 0, w = 0;
-#pragma unroll
-  for (int j = 0; j < Obs<MM>::n; ++j) {  // kLds: the LDS copy against the kernarg table
-    if (ocx<MM>(p, j) != q->cx[j]) { bad = 40 + j; v = ocx<MM>(p, j); w = q->cx[j]; }
-    if (ocy<MM>(p, j) != q->cy[j]) { bad = 50 + j; v = ocy<MM>(p, j); w = q->cy[j]; }
-    if (or2<MM>(p, j) != q->r2[j]) { bad = 60 + j; v = or2<MM>(p, j); w = q->r2[j]; }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    if (__builtin_bit_cast(unsigned long long, (double)p.cx[j]) != __builtin_bit_cast(unsigned long long, (double)q->cx[j])) { bad = j; v = p.cx[j]; w = q->cx[j]; }
-    if (__builtin_bit_cast(unsigned long long, (double)p.cy[j]) != __builtin_bit_cast(unsigned long long, (double)q->cy[j])) { bad = 10 + j; v = p.cy[j]; w = q->cy[j]; }
-    if (__builtin_bit_cast(unsigned long long, (double)p.r2[j]) != __builtin_bit_cast(unsigned long long, (double)q->r2[j])) { bad = 20 + j; v = p.r2[j]; w = q->r2[j]; }
-  }
-  if (p.dt != q->dt) { bad = 30; v = p.dt; w = q->dt; }
-  if (p.umax0 != q->umax0 || p.umin0 != q->umin0 || p.umax1 != q->umax1 || p.umin1 != q->umin1) { bad = 31; v = p.umax0; w = q->umax0; }
-  if (p.neg_beta != q->neg_beta || p.neg_inv_beta != q->neg_inv_beta) { bad = 32; v = p.neg_beta; w = q->neg_beta; }
-  if (p.eps != q->eps) { bad = 33; v = p.eps; w = q->eps; }
-  if (p.N != q->N) { bad = 34; v = p.N; w = q->N; }
-  if (bad >= 0)
-    printf("DIAG const blk=%d thr=%d where=%d it=%d field=%d have=%.17g want=%.17g\n", (int)blockIdx.x,
-           (int)threadIdx.x, where, it, bad, (double)v, (double)w);
-}
-#define DIAG_P(MM, p, where, it) diag_p<MM>(p, where, it)
-#else
-#define DIAG_P(MM, p, where, it) ((void)0)
 #endif
 
 // P = 4 tape slots: slot q of the solve's X / U records at lane offset base + q * stride
@@ -2553,19 +2084,12 @@ __device__ __forceinline__ int ilqr(const FP& p, const FCost& c, const FIlqr& cf
   int st = 0;
   int cur = kSlotInit;  // P = 4: the current tape's slot
   pf.mark(ph);
-  DIAG_P(M, p, TRACK ? 100 : 0, -1);
   for (int it = 0; it < cf.max_iter; ++it) {
     iters = it + 1;
     if (!backward<TRACK, M>(p, c, cf.reg, S, h)) {
       st = DTMPC_ST_NONFINITE;
-#ifdef DTMPC_FAST_DIAG
-      printf("DIAG backward non-finite blk=%d thr=%d h=%d trk=%d it=%d x0=(%.17g %.17g %.17g %.17g)\n", (int)blockIdx.x,
-             (int)threadIdx.x, h, (int)TRACK, it, (double)x0[0], (double)x0[1], (double)x0[2], (double)x0[3]);
-      DIAG_P(M, p, TRACK ? 101 : 1, it);
-#endif
       break;
     }
-    DIAG_P(M, p, TRACK ? 102 : 2, it);
     pf.mark(ph + 1);
     real bestJ, al;
     int bc;
@@ -2586,15 +2110,8 @@ __device__ __forceinline__ int ilqr(const FP& p, const FCost& c, const FIlqr& cf
 #endif
     if (best < 0) {
       st = DTMPC_ST_NONFINITE;
-#ifdef DTMPC_FAST_DIAG
-      printf("DIAG line search non-finite blk=%d thr=%d h=%d trk=%d it=%d Jprev=%.17g bestJ=%.17g x0=(%.17g %.17g %.17g %.17g)\n",
-             (int)blockIdx.x, (int)threadIdx.x, h, (int)TRACK, it, (double)Jcur, (double)bestJ, (double)x0[0],
-             (double)x0[1], (double)x0[2], (double)x0[3]);
-      DIAG_P(M, p, TRACK ? 103 : 3, it);
-#endif
       break;
     }
-    DIAG_P(M, p, TRACK ? 104 : 4, it);
     if (ch && h == 0) ch[it * chs] = (signed char)best;
     if (al != 0.f) {
       if (P == 4) {
@@ -2809,26 +2326,16 @@ __device__ __forceinline__ KArg* kargs() {
   return (KArg*)k;  // generic; the compiler infers the constant address space back (scalar loads)
 }
 
-#ifdef DTMPC_FAST_GLOBAL
-__device__ __forceinline__ const char* kargs_ws() { return (const char*)kargs()->a.work; }
-#endif
-
-#ifndef DTMPC_FAST_PIN
-#define DTMPC_FAST_PIN 1
-#endif
-#ifndef DTMPC_FAST_PIN64_MAX
-#define DTMPC_FAST_PIN64_MAX 5
-#endif
 // the problem constants of one phase; the obstacle table pinned in VGPRs (every candidate of every
 // step reads it; in scalar registers it is what the compiler would spill first).  f64 pins at most five
 // obstacles (30 VGPRs; the paper's M = 5): the f64 receding kernel at M = 8 with its 48-VGPR table spilled
 // into scratch inside its per-lane divergent loops and returned run-to-run different results (NaN on one
 // box, 55 % of the runs off on another; unchanged by -ftrivial-auto-var-init, gone with the table
 // unpinned -- DESIGN.md section 9, profiles/r04/m8_receding.txt); f64 at M = 5 runs 13.6 ms pinned, 15.6 unpinned.
+constexpr int kPin64Max = 5;
 template <int M>
 __device__ __forceinline__ FP pin_p(FP p) {
-#if DTMPC_FAST_PIN
-  if (Obs<M>::lds || (DTMPC_FAST_F64 && Obs<M>::n > DTMPC_FAST_PIN64_MAX)) return p;
+  if (Obs<M>::reread || (DTMPC_FAST_F64 && Obs<M>::n > kPin64Max)) return p;
 #pragma unroll
   for (int j = 0; j < Obs<M>::n; ++j) {
     real vx = p.cx[j], vy = p.cy[j], vr = p.r2[j];
@@ -2839,7 +2346,6 @@ __device__ __forceinline__ FP pin_p(FP p) {
     p.cy[j] = vy;
     p.r2[j] = vr;
   }
-#endif
   return p;
 }
 template <int M>
@@ -2850,43 +2356,32 @@ __device__ __forceinline__ FP phase_p() {
 // Where an f64 instantiation keeps its obstacle table (round 5).  Every f64 fused kernel must run without a
 // private segment (build.py check_resources: the f64 defects of rounds 3-4 all came from f64 kernels that kept
 // values in scratch inside per-lane divergent loops).  The table pinned in VGPRs (pin_p) fits
-// beside the compact gamma = 0 records up to DTMPC_FAST_PIN64_MAX obstacles; the general records (GM = 0, and the
-// general path's solves, which hold both record forms) and larger tables read it again at each use (kLds) -- by a
-// scalar load of the kernarg segment's copy (DTMPC_FAST64_TABSRC = 1, the default; 0 is the LDS copy, A/B only).
-// DTMPC_FAST64_TAB: 1 that rule (default), 2 kLds in every f64 kernel, 0 never kLds (the round-4 forms, A/B).
-#ifndef DTMPC_FAST64_TAB
-#define DTMPC_FAST64_TAB 1
-#endif
+// beside the compact gamma = 0 records up to kPin64Max obstacles; the general records (GM = 0, and the
+// general path's solves, which hold both record forms) and larger tables read it again at each use (kReread) -- by a
+// scalar load of the kernarg segment's copy (profiles/r05/ab_f64_table.txt).
 template <int M, int GM>
 constexpr int tab_flag();
 // the exp form of an f64 instantiation: the one-block asm polynomial holds its ten coefficients in VGPRs, which the
-// table-in-kernarg (kLds) kernels and the four-lane kernels cannot afford without a private segment (build.py check:
+// table-in-kernarg (kReread) kernels and the four-lane kernels cannot afford without a private segment (build.py check:
 // 48 B of scratch in fk64::tube_fast_kernel<5, 4, 2> beside the in-step broadcast of the backward inputs, in <5, 4, 1>
 // without it), so it runs at one and two lanes.  Round 5 kept it at one lane after the two-lane
 // form read stale values on one trajectory of 700; round 6 found the cause (profiles/r06/flow_copy_root_cause.txt): the
 // register allocator's live-range-split copies in the flow block of dbarrier's divergent if / else, which ran with the
 // then-lanes' exec mask only -- the asm form's extra VGPRs only made the allocator split there.  dbarrier is branchless
 // in f64 now, build.py fails a build with any such copy (scan_flow_copies), and the two-lane asm form (and the
-// four-lane one, where it fits) passes tests/test_gpu_reuse.py (profiles/r06/logs).
-#ifndef DTMPC_FAST64_XASM_MAXP
-#define DTMPC_FAST64_XASM_MAXP 2
-#endif
+// four-lane one, where it fits) passes tests/test_gpu_reuse.py (profiles/r06/logs).  The four-lane form with the
+// compact records fits only by spilling, which the build's resource check refuses, so the rule is P <= 2.
 template <int M, int GM, int P>
 constexpr int xasm_flag() {
 #if DTMPC_FAST_F64
-  return (DTMPC_FAST64_EXP == 3 && P <= DTMPC_FAST64_XASM_MAXP && (P <= 2 || GM == 2) && tab_flag<M, GM>() == 0)
-             ? kXasm
-             : 0;
+  return (P <= 2 && tab_flag<M, GM>() == 0) ? kXasm : 0;
 #else
   return 0;
 #endif
 }
 template <int M, int GM>
 constexpr int tab_flag() {
-  return (DTMPC_FAST_F64 && (DTMPC_FAST64_TAB == 2 ||
-                             (DTMPC_FAST64_TAB == 1 && (GM == 0 || Obs<M>::n > DTMPC_FAST_PIN64_MAX))))
-             ? kLds
-             : 0;
+  return (DTMPC_FAST_F64 && (GM == 0 || Obs<M>::n > kPin64Max)) ? kReread : 0;
 }
 
 // GM: 0 general, 1 gamma = 0 gain records, 2 gamma = 0 gain records + Riccati step (the default at gamma = 0),
@@ -2912,7 +2407,9 @@ tube_fast_kernel(FK kk) {
     const int n = kargs()->a.stagger * (int)(blockIdx.x & 7) / 8;
     for (int r = 0; r < n; ++r) __builtin_amdgcn_s_sleep(127);
   }
-  obs_fill<ML>(kargs()->p);
+  // (an opaque copy of the kernarg pointer left by the removed LDS table fill: it is one s_mov at kernel entry, and
+  // dropping it moves the register allocation of the whole kernel -- for a change that may move device code)
+  (void)kargs();
   Prof pf;
   pf.start();
   if (t < Bc) {
@@ -3017,7 +2514,6 @@ tube_fast_kernel(FK kk) {
       const RA A8{K->a.oA8, cb * (32u * ES), l32}, A2{K->a.oA2, cb * (8u * ES), l8};
       const FP p = phase_p<ML>();
       st |= sensitivity<ML>(p, ca, Sa, A8, A2, acc);
-      DIAG_P(ML, p, 200, st);
     }
     pf.mark(9);
     {  // plant step with disturbance, nominal propagation (:990-1001), log, warm-start shift
@@ -3075,10 +2571,6 @@ tube_fast_kernel(FK kk) {
         a.bbar[i] = qb;
       }
       acc[7] = 1.f;
-      DIAG_P(ML, p, 300, st);
-#ifdef DTMPC_FAST_DIAG
-      if (st && h == 0) printf("DIAG status traj=%d st=%d itn=%d ita=%d\n", i, st, itn, ita);
-#endif
       // healthy trajectories only (status 0 and every gradient component within the bound, NaN failing
       // the test); a trajectory's lanes count once
       real gm = m_abs(acc[1]);
@@ -3227,7 +2719,7 @@ ilqr_fast_kernel(IK kk) {
   (void)kk;  // read through ikargs()
   const IArgs& a = ikargs()->a;
   constexpr int ML = M | tab_flag<M, GM>() | xasm_flag<M, GM, P>();
-  obs_fill<ML>(ikargs()->p);
+  (void)ikargs();  // as in tube_fast_kernel
   const int B = a.B, Bc = a.Bc, i0 = a.i0;
   const int gl = blockIdx.x * blockDim.x + threadIdx.x;
   const int t = gl / P, h = gl % P;
@@ -3355,7 +2847,7 @@ receding_fast_kernel(RK kk) {
   constexpr int ML = M | tab_flag<M, GM>() | xasm_flag<M, GM, 1>();
   constexpr int MW = ML | kWrap;
   (void)kk;  // read through rkargs()
-  obs_fill<ML>(rkargs()->p);
+  (void)rkargs();  // as in tube_fast_kernel
   const RArgs& a = rkargs()->a;
   const int B = a.B, Bc = a.Bc, i0 = a.i0;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3508,7 +3000,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 
 general_solve_fast_kernel(GSK kk) {
   (void)kk;  // read through gskargs()
   constexpr int ML = M | tab_flag<M, 0>();  // both record forms in one kernel: placed as the general records
-  obs_fill<ML>(gskargs()->p);
+  (void)gskargs();  // as in tube_fast_kernel
   const GSArgs& a = gskargs()->a;
   const int B = a.B, Bc = a.Bc, i0 = a.i0;
   const int gl = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3715,22 +3207,6 @@ static bool tube_fast_scc(int N, int64_t B, int64_t Bc, int lanes, int g0) {
 }
 #endif
 
-#if DTMPC_FAST_F64
-// f64 general gain records at four lanes.  Round 5 v2 ran them on the generic f64 kernel: the fused form gave
-// run-to-run different results at some obstacle counts and not at others, moving with every change of the kernel.
-// The cause was the store-data hazard of the 128-bit record stores (st128; every f64 record store is 128-bit):
-// since v3 the family runs fused (scripts/diag_records.py: every M = 1-8 at four lanes within 1e-8 of the generic
-// kernel, twice bitwise equal; profiles/r05/diag_records_v3.txt).  DTMPC_FAST64_L4G=0 routes it to the generic
-// kernel again (A/B only).
-bool tube_fast_lanes_ok64(const dtmpc_spec* sp, int lanes) {
-  static const bool generic = [] {
-    const char* e = getenv("DTMPC_FAST64_L4G");
-    return e && e[0] == '0';
-  }();
-  return !(generic && lanes == 4 && fast_g0(sp) == 0);
-}
-#endif
-
 int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_t B, int64_t goff, int64_t step,
                      const dtmpc_tube_state* S, const void* w, hipStream_t st) {
   FK_NS::FK kk;
@@ -3777,9 +3253,6 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
   // keeps the general records and recursion, = 1 the compact records with the general recursion: the
   // tests compare 1 with 0 for exact equality (records) and the default with the oracle builds.
   const int g0 = fast_g0(sp);
-#if DTMPC_FAST_F64
-  if (!tube_fast_lanes_ok64(sp, lanes)) return set_err(DTMPC_ERR_BAD_ARG, "f64 general records at four lanes run the generic kernel");
-#endif
   {
     const char* e = getenv("DTMPC_FAST_STAGGER");  // sleep rounds of ~8.1k cycles (A/B; default 0)
     a.stagger = e ? atoi(e) : 0;

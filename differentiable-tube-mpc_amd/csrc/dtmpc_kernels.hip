@@ -823,7 +823,7 @@ int dtmpc_tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg
                                       "chunk of the precision (dtmpc_tube_split_ok)");
   hipStream_t st = (hipStream_t)stream;
   if (tube_fast_eligible(dtype, spec, cfg)) return launch_tube_fast(spec, cfg, B, global_offset, step, S, w, st);
-  if (tube_fast_eligible64(dtype, spec, cfg) && tube_fast_lanes_ok64(spec, S->lanes))
+  if (tube_fast_eligible64(dtype, spec, cfg))
     return launch_tube_fast64(spec, cfg, B, global_offset, step, S, w, st);
   if (dtype == DTMPC_F32) return launch_tube<float>(spec, cfg, B, global_offset, step, S, w, st);
   if (dtype == DTMPC_F64) return launch_tube<double>(spec, cfg, B, global_offset, step, S, w, st);
@@ -832,8 +832,8 @@ int dtmpc_tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg
 
 int32_t dtmpc_tube_split_supported(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg, int32_t lanes) {
   if (!spec || !cfg) return 0;
-  return (tube_fast_eligible(dtype, spec, cfg) ||
-          (tube_fast_eligible64(dtype, spec, cfg) && tube_fast_lanes_ok64(spec, lanes))) ? 1 : 0;
+  (void)lanes;  // every lane count of either precision runs fused
+  return (tube_fast_eligible(dtype, spec, cfg) || tube_fast_eligible64(dtype, spec, cfg)) ? 1 : 0;
 }
 
 // ABI 7: the split needs the nominal records of the WHOLE batch between the two launches, i.e. one launch

@@ -36,7 +36,6 @@ __device__ __forceinline__ pf2 pk_log(pf2 x) {  // m_log per element, the scalin
 // m_sincos (dtmpc_device.hpp) on a pair: sincos_cw with every fma / mul packed; the rare element
 // outside |x| <= 65536 (or non-finite) sends the pair through the scalar function
 __device__ __forceinline__ void pk_sincos(pf2 x, pf2& sn, pf2& cs) {
-#ifndef DTMPC_OCML_SINCOS
   if (__builtin_expect(__builtin_fabsf(x.x) <= 65536.0f && __builtin_fabsf(x.y) <= 65536.0f, 1)) {
     const pf2 q = pf2{__builtin_rintf(x.x * k2oPi), __builtin_rintf(x.y * k2oPi)};
     pf2 r = __builtin_elementwise_fma(-q, pf2(kPio2A), x);
@@ -56,7 +55,6 @@ __device__ __forceinline__ void pk_sincos(pf2 x, pf2& sn, pf2& cs) {
     cs = pf2{((j0 + 1) & 2) ? -co0 : co0, ((j1 + 1) & 2) ? -co1 : co1};
     return;
   }
-#endif
   float s0, c0, s1, c1;
   m_sincos(x.x, &s0, &c0);
   m_sincos(x.y, &s1, &c1);

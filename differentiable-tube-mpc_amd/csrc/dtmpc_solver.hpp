@@ -662,10 +662,6 @@ __device__ __forceinline__ int ilqr_traj(const DSpec<T>& s, const DCost<T>& c, c
   for (int it = 0; it < cfg.max_iter; ++it) {
     iters = it + 1;
     if (!ilqr_backward(s, c, cfg.reg, X, U, gains, Xr, rf, Ur)) return DTMPC_ST_NONFINITE;
-#ifdef DTMPC_DIAG_BW2  // timing attribution only: the pass again (idempotent)
-    __asm__ volatile("" ::: "memory");
-    if (!ilqr_backward(s, c, cfg.reg, X, U, gains, Xr, rf, Ur)) return DTMPC_ST_NONFINITE;
-#endif
     pr.mark(pb + 1);
     T bestJ, al;
     int best;
@@ -675,18 +671,10 @@ __device__ __forceinline__ int ilqr_traj(const DSpec<T>& s, const DCost<T>& c, c
       best = line_search_pk<NA>(s, c, cfg, x0, Bc0, X, U, gains, Xr, rf, Ur, Jcur, bestJ, al);
     else
       best = line_search<T, NA>(s, c, cfg, x0, Bc0, X, U, gains, Xr, rf, Ur, Jcur, bestJ, al);
-#ifdef DTMPC_DIAG_LS2  // timing attribution only: the pass again (same decision)
-    __asm__ volatile("" ::: "memory");
-    best = line_search<T, NA>(s, c, cfg, x0, Bc0, X, U, gains, Xr, rf, Ur, Jcur, bestJ, al);
-#endif
     pr.mark(pb + 2);
     if (best < 0) return DTMPC_ST_NONFINITE;
     if (ch && h == 0) ch[it * chs] = (signed char)best;
     if (al != T(0)) commit_candidate(s, al, x0, Bc0, X, U, gains);
-#ifdef DTMPC_DIAG_CM2  // timing attribution only: a second rollout (results change)
-    __asm__ volatile("" ::: "memory");
-    if (al != T(0)) commit_candidate(s, al, x0, Bc0, X, U, gains);
-#endif
     Jcur = bestJ;
     pr.mark(pb + 3);
     // :303-305

@@ -1,7 +1,7 @@
 """The lane forms of the fused solver compute the same numbers (GPU).  One, two and four lanes per trajectory split the
 line search's candidates and the backward pass's linearisation differently, but every value is produced by the same
 operations in the same order; since round 6 the backward step (the Jacobian and the Riccati step) compiles without
-implicit FMA contraction, every multiply-add an explicit fma at a fixed place (DTMPC_FAST_RIC_FMA), so the compiler
+implicit FMA contraction, every multiply-add an explicit fma at a fixed place (rfm / fma2 in dtmpc_fast.hip), so the compiler
 cannot round it differently per form (reference core/ddp.py:213-254).
 Two closed-loop steps of the paper setup (fixed iterations, B = 700, theta held) at 1, 2 and 4 lanes: every state,
 tape, log row (the per-trajectory DOC gradient rows included) and status bitwise equal; the standalone batched iLQR (core.ddp.ilqr_solve, BASELINE config 2's solve) the
