@@ -3,7 +3,7 @@
 Plain hipcc, no build system: the translation units compiled in parallel, then linked --
 csrc/dtmpc_kernels.hip (paper path + per-function entry points), csrc/dtmpc_fast.hip (the fused tube step of
 the paper configuration), csrc/dtmpc_fast_ilqr.hip (its solver as the standalone batched iLQR), csrc/dtmpc_fast_general.hip (the
-general path's solves on it), csrc/dtmpc_general.hip (general IFT
+general path's solves on it), csrc/dtmpc_fast_scenes.hip (both with per-trajectory scenes), csrc/dtmpc_general.hip (general IFT
 path), csrc/dtmpc_receding.hip (receding-horizon nominal MPC driver), csrc/dtmpc_control.hip (tanh-box
 control map + cost derivatives), csrc/dtmpc_ocp.hip (tape cost of core/ocp.py), csrc/dtmpc_systems.hip
 (per-point kernels of the reference's per-function API: dynamics, h, barriers, Jacobians, clamp, cost
@@ -20,7 +20,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", f)
         for f in ("dtmpc_kernels.hip", "dtmpc_fast.hip", "dtmpc_fast_ilp.hip", "dtmpc_fast64.hip", "dtmpc_fast64_ilp.hip",
-                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
+                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
                   "dtmpc_control.hip", "dtmpc_ocp.hip", "dtmpc_systems.hip")]
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("dtmpc_device.hpp", "dtmpc_solver.hpp", "dtmpc_general.hpp",
                                                  "dtmpc_host.hpp", "dtmpc_ls_pk.hpp")] + [
@@ -35,9 +35,12 @@ FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno-
 # the f32 two-lane ones with LLVM's iterative ILP scheduler -- same-box A/B in profiles/r06/ab_sched.txt; the four-lane
 # forms lost with it
 # and the f32 standalone-iLQR / receding unit (config 2 -1.3 %, receding -0.8 %; its f64 twin lost 1.2 % and keeps the
-# default) and the f32 general-path unit (general IFT step -1.1 %)
+# default) and the f32 general-path unit (general IFT step -1.1 %); the per-trajectory-scenes unit follows its
+# shared twins: the one- and two-lane tube kernels and every standalone-iLQR form are built with it there (its
+# four-lane tube kernels ride along, not measured apart)
 UNIT_FLAGS = {u: ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-              for u in ("dtmpc_fast_ilp", "dtmpc_fast64_ilp", "dtmpc_fast_ilqr", "dtmpc_fast_general")}
+              for u in ("dtmpc_fast_ilp", "dtmpc_fast64_ilp", "dtmpc_fast_ilqr", "dtmpc_fast_general",
+                        "dtmpc_fast_scenes")}
 
 
 def _lib_key() -> str:

@@ -27,7 +27,8 @@
 
 // this file is the tube step's translation unit; dtmpc_fast_ilqr.hip / dtmpc_fast_general.hip include it
 // for the standalone iLQR's and the general path's instantiations (their host parts below)
-#if defined(DTMPC_FAST_ILQR_TU) || defined(DTMPC_FAST_GENERAL_TU) || defined(DTMPC_FAST_ILP_TU)
+#if defined(DTMPC_FAST_ILQR_TU) || defined(DTMPC_FAST_GENERAL_TU) || defined(DTMPC_FAST_ILP_TU) || \
+    defined(DTMPC_FAST_SCENES_TU)
 #define DTMPC_FAST_AUX_TU 1
 #endif
 // The one-lane tube kernels (the headline's form) and the f32 two-lane ones live in their own translation units
@@ -105,6 +106,11 @@ constexpr int kReread = 64;
 // kXasm (f64): the smooth-min exp's polynomial as one inline-assembly block (exp_sm<true>) -- set only where it
 // fits the register file without a private segment (xasm_flag below); elsewhere the same fmas compiled normally.
 constexpr int kXasm = 128;
+// kScene (f32): per-trajectory scenes -- at each phase start a lane fills the pinned table (and the nominal target) from
+// its own column of the scenes array [3M + 3][B] (rows cx, cy, r2, then target x, y, heading; dtmpc_tube_state.scenes)
+// instead of the kernarg block's copy (scene_p below).  Everything after the phase start reads the same registers, so
+// the step loops are the shared form's; only csrc/dtmpc_fast_scenes.hip instantiates it.
+constexpr int kScene = 256;
 template <int M>
 struct Obs {
   static constexpr int n = M & (kTight - 1);
@@ -112,6 +118,7 @@ struct Obs {
   static constexpr bool wrap = (M & kWrap) != 0;
   static constexpr bool reread = (M & kReread) != 0;
   static constexpr bool xasm = (M & kXasm) != 0;
+  static constexpr bool scene = (M & kScene) != 0;
 };
 
 // obstacle i of the table: the registers of FP, or (kReread) loaded again at each use -- through an opaque pointer
@@ -185,6 +192,7 @@ struct FArgs {
   signed char* choices;  // [nom max_iter + aux max_iter][B] or NULL (dtmpc_tube_state.choices)
   real gbound;          // health bound on the gradient row (dtmpc_tube_cfg.grad_bound; +inf: none)
   real* costs;          // [nom max_iter + aux max_iter][8][B] or NULL (dtmpc_tube_state.costs)
+  const real* scenes;   // [3M + 3][B] or NULL (dtmpc_tube_state.scenes): read by the kScene instantiations only
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -2352,6 +2360,36 @@ template <int M>
 __device__ __forceinline__ FP phase_p() {
   return pin_p<M>(kargs()->p);
 }
+// kScene: trajectory i's own table -- i its index in the WHOLE batch (the launch chunk's i0 + the index in the chunk),
+// nb the batch, the stride of the scenes rows.  3M coalesced loads (one 256 B line per row per wave) into the registers
+// pin_p then pins; the values are what make_spec puts in the kernarg block for a spec with this scene's obstacles.
+template <int M>
+__device__ __forceinline__ FP scene_p(FP p, const real* sc, size_t nb, int i) {
+  constexpr int n = Obs<M>::n;
+  const real* q = sc + i;
+#pragma unroll
+  for (int j = 0; j < n; ++j) {
+    p.cx[j] = q[(size_t)j * nb];
+    p.cy[j] = q[(size_t)(n + j) * nb];
+    p.r2[j] = q[(size_t)(2 * n + j) * nb];
+  }
+  return p;
+}
+// ... and its nominal target (rows 3M .. 3M + 2); a tracking cost keeps its zero target
+template <int M>
+__device__ __forceinline__ f4 scene_tg(const real* sc, size_t nb, int i) {
+  constexpr int n = Obs<M>::n;
+  const real* q = sc + i;
+  return f4{q[(size_t)(3 * n) * nb], q[(size_t)(3 * n + 1) * nb], q[(size_t)(3 * n + 2) * nb], 0.f};
+}
+// the kScene phase start of trajectory i of the tube step.  (The kernels choose between this and phase_p<M>() by a
+// constant condition at the call, so that the shared instantiations compile from exactly the text they had: an extra
+// by-value hop of FP / FCost through a helper moved their register allocation.)
+template <int M>
+__device__ __forceinline__ FP phase_ps(int i) {
+  KArg* K = kargs();
+  return pin_p<M>(scene_p<M>(K->p, K->a.scenes, (size_t)K->a.B, i));
+}
 
 // Where an f64 instantiation keeps its obstacle table (round 5).  Every f64 fused kernel must run without a
 // private segment (build.py check_resources: the f64 defects of rounds 3-4 all came from f64 kernels that kept
@@ -2462,11 +2500,16 @@ tube_fast_kernel(FK kk) {
       Sn.G.k = RA{K->a.ok, cb * (8u * ES), l8};
       Sn.X = Soa<4>{(char*)K->a.Xnom, 4u * bb, L};
       Sn.U = Soa<2>{(char*)K->a.Unom, 2u * bb, L};
-      const FP p = phase_p<ML>();
+      const FP p = Obs<ML>::scene ? phase_ps<ML>(i) : phase_p<ML>();
       const FCost cn = K->cn;
       const FIlqr cfn = K->cfn;
       const real xn0[4] = {y0, y1, y2, yb};
       const DecRec dr{K->a.choices ? K->a.choices + i : nullptr, K->a.costs ? K->a.costs + i : nullptr, nb};
+      if constexpr (Obs<ML>::scene) {  // the trajectory's own target
+        FCost cs = cn;
+        cs.tg = scene_tg<ML>(K->a.scenes, nb, i);
+        st |= ilqr<false, ML, P>(p, cs, cfn, xn0, Sn, h, sm, itn, pf, dr);
+      } else
       st |= ilqr<false, ML, P>(p, cn, cfn, xn0, Sn, h, sm, itn, pf, dr);
     }
     if (phase == 1) {  // hand over to the phase-2 launch; the plant state and theta are untouched
@@ -2501,7 +2544,7 @@ tube_fast_kernel(FK kk) {
       Sa.G.k = RA{K->a.ok, cb * (8u * ES), l8};
       Sa.X = Soa<4>{(char*)K->a.Xaux, 4u * bb, L};
       Sa.U = Soa<2>{(char*)K->a.Uaux, 2u * bb, L};
-      const FP p = phase_p<ML>();
+      const FP p = Obs<ML>::scene ? phase_ps<ML>(i) : phase_p<ML>();
       const FIlqr cfa = K->cfa;
       const real xa0[4] = {x0, x1, x2, xb};
       const size_t o = (size_t)K->cfn.max_iter * nb + i;
@@ -2512,14 +2555,14 @@ tube_fast_kernel(FK kk) {
     {  // upper loss, DOC sensitivity and gradient (:915-976)
       KArg* K = kargs();
       const RA A8{K->a.oA8, cb * (32u * ES), l32}, A2{K->a.oA2, cb * (8u * ES), l8};
-      const FP p = phase_p<ML>();
+      const FP p = Obs<ML>::scene ? phase_ps<ML>(i) : phase_p<ML>();
       st |= sensitivity<ML>(p, ca, Sa, A8, A2, acc);
     }
     pf.mark(9);
     {  // plant step with disturbance, nominal propagation (:990-1001), log, warm-start shift
       KArg* K = kargs();
       const FArgs& a = K->a;
-      const FP p = phase_p<ML>();
+      const FP p = Obs<ML>::scene ? phase_ps<ML>(i) : phase_p<ML>();
       // the plans' first controls, from the records (the ABI tapes already hold the shifted warm starts)
       const f2 ua = rld2(Sa.r, Sa.UA, 0, 0), un = rld2(Sa.r, Sn.UA, 0, 0);
       const real u0 = ua.x, u1 = ua.y;
@@ -2698,6 +2741,7 @@ struct IArgs {
   real* costs;
   real* work;
   unsigned wsz, oX, oU, oK, ok, oXR, oUR;
+  const real* scenes;  // [3M + 3][B] or NULL (dtmpc_ilqr_solve_scenes): read by the kScene instantiations only
 };
 struct IK {
   FP p;
@@ -2742,7 +2786,7 @@ ilqr_fast_kernel(IK kk) {
   S.G.k = RA{a.ok, cb * (8u * ES), l8};
   S.X = Soa<4>{(char*)a.X, 4u * bb, L};
   S.U = Soa<2>{(char*)a.U, 2u * bb, L};
-  const FP p = pin_p<ML>(ikargs()->p);
+  const FP p = Obs<ML>::scene ? pin_p<ML>(scene_p<ML>(ikargs()->p, a.scenes, nb, i)) : pin_p<ML>(ikargs()->p);
   const int N = p.N;
   if (TRACK) {  // the references into records (the lanes of a trajectory split the rows; one wave: in order)
     for (int k = h; k <= N; k += P) {
@@ -2761,7 +2805,14 @@ ilqr_fast_kernel(IK kk) {
   int it = 0;
   Prof pf;
   pf.start();
-  const int st = ilqr<TRACK, ML, P, false>(p, c, cf, x0, S, h, sm, it, pf, dr);
+  int st;
+  if constexpr (Obs<ML>::scene && !TRACK) {  // the trajectory's own target (a tracking cost has none)
+    FCost cs = c;
+    cs.tg = scene_tg<ML>(a.scenes, nb, i);
+    st = ilqr<TRACK, ML, P, false>(p, cs, cf, x0, S, h, sm, it, pf, dr);
+  } else {
+    st = ilqr<TRACK, ML, P, false>(p, c, cf, x0, S, h, sm, it, pf, dr);
+  }
   // the last backward pass's gains out to the ABI arrays (G0 records: K's barrier column is exactly 0);
   // max_iter = 0: no backward pass ran and the records were never written -- zeros, as the generic kernel
   // leaves the zeroed arrays
@@ -3123,6 +3174,13 @@ int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, 
                               const FK_NS::FK& kk);
 #endif
 
+#if !DTMPC_FAST_F64
+// the per-trajectory-scene launches (csrc/dtmpc_fast_scenes.hip: the kScene instantiations, M obstacles at the
+// gamma = 0 record form): the tube step with kk.a.scenes set, the standalone iLQR with kk.a.scenes set
+int launch_tube_fast_scenes(int M, int lanes, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FK& kk);
+int launch_ilqr_fast_scenes(int M, int lanes, bool track, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::IK& kk);
+#endif
+
 #ifndef DTMPC_FAST_AUX_TU  // the tube step (this file's own translation unit)
 
 // The fast kernel's configuration: f32, smooth-min over 1..8 obstacles, relaxed inverse barrier,
@@ -3238,6 +3296,9 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
   a.w = (const real*)w;
   a.choices = (signed char*)S->choices;
   a.costs = (real*)S->costs;
+  a.scenes = (const real*)S->scenes;
+  if (a.scenes && (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0))  // dtmpc_tube_step has refused these (scenes_unsupported)
+    return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes need f32 and dbas_gamma == 0");
   a.gbound = cf->grad_bound > 0 ? real(cf->grad_bound) : real(__builtin_inf());
   a.disturbance = cf->disturbance;
   a.write_log = (cf->write_log && S->log) ? 1 : 0;
@@ -3291,6 +3352,12 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
     }
 #endif
     (void)gk;
+#if !DTMPC_FAST_F64
+    if (a.scenes) {  // per-trajectory scenes: the kScene kernels' unit (the gamma = 0 record form, no sin / cos cache)
+      if (int r = launch_tube_fast_scenes(sp->n_obstacles, lanes, grid, (unsigned)bs, st, kk)) return r;
+      continue;
+    }
+#endif
 #define FAST_LAUNCH(m, l, g) \
   hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) == 3 ? shm : 0u, st, kk)
 #define FAST_LANES(m, l) \
@@ -3419,9 +3486,12 @@ bool FKN(ilqr_fast_eligible)(int dtype, const dtmpc_spec* sp, const dtmpc_cost* 
 
 int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmpc_ilqr_cfg* cf, int64_t B, const void* x0,
                      const void* Xref, const void* Uref, void* X, void* U, void* K, void* kff, int* iters, int* status,
-                     signed char* choices, void* costs, int lanes, void* work, size_t work_bytes, hipStream_t st) {
+                     signed char* choices, void* costs, int lanes, void* work, size_t work_bytes, hipStream_t st,
+                     const void* scenes) {
   const int N = sp->horizon;
   if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "lanes must be 1, 2 or 4");
+  if (scenes && (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0))  // dtmpc_ilqr_solve_scenes has refused these
+    return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes need f32 and dbas_gamma == 0");
   if (!work || work_bytes < FKN(ilqr_fast_workspace_bytes)(N, B, lanes))
     return set_err(DTMPC_ERR_BAD_ARG, "work_bytes < dtmpc_ilqr_workspace_bytes(...)");
   FK_NS::IK kk;
@@ -3446,6 +3516,7 @@ int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmp
   a.choices = choices;
   a.costs = (real*)costs;
   a.work = (real*)work;
+  a.scenes = (const real*)scenes;
   // gamma = 0: the compact gain records and the Riccati step without the barrier state's column
   const int g0 = kk.p.gamma == 0.f ? 2 : 0;
   const int64_t chunk = FKN(ilqr_fast_chunk_max)(N, lanes);
@@ -3463,6 +3534,12 @@ int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmp
     a.wsz = a.oUR + (unsigned)(Bc * N * 8 * ES);
     const int bs = tube_block(B, lanes);
     const dim3 grid = dim3((unsigned)((Bc * lanes + bs - 1) / bs));
+#if !DTMPC_FAST_F64
+    if (a.scenes) {  // per-trajectory scenes: the kScene kernels' unit
+      if (int r = launch_ilqr_fast_scenes(sp->n_obstacles, lanes, track, grid, (unsigned)bs, st, kk)) return r;
+      continue;
+    }
+#endif
 #define IL_LAUNCH(m, l, t, g) hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<m, l, t, g>), grid, dim3(bs), 0, st, kk)
 #define IL_G(m, l, t) \
   if (g0 == 2) IL_LAUNCH(m, l, t, 2); else IL_LAUNCH(m, l, t, 0);
@@ -3563,6 +3640,69 @@ int FKN(launch_receding_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const 
   }
   return check_launch("receding_fast_kernel");
 }
+
+#elif defined(DTMPC_FAST_SCENES_TU)  // the per-trajectory-scene kernels (csrc/dtmpc_fast_scenes.hip), f32 only
+
+// Why a scenes pointer cannot be honoured for this precision / problem / line search, or NULL when it can
+// (dtmpc_scenes_supported): the kScene kernels exist in f32 for the fused configuration at dbas_gamma == 0.
+const char* scenes_unsupported(int dtype, const dtmpc_spec* sp, const dtmpc_ilqr_cfg* cf) {
+  if (dtype != DTMPC_F32) return "per-trajectory scenes: f32 only";
+  if (sp->obs_aggregation != DTMPC_OBS_SMOOTHMIN) return "per-trajectory scenes: smooth-min obstacle aggregation only";
+  if (sp->n_obstacles < 1 || sp->n_obstacles > 8) return "per-trajectory scenes: 1 to 8 obstacles";
+  if (sp->barrier_type != DTMPC_BARRIER_INVERSE) return "per-trajectory scenes: relaxed inverse barrier only";
+  if (sp->dbas_gamma != 0.0) return "per-trajectory scenes: dbas_gamma must be 0";
+  if (sp->h_offset != 0.0) return "per-trajectory scenes: h_offset must be 0";
+  if (cf->n_alphas < 1 || cf->n_alphas > DTMPC_MAX_ALPHAS) return "per-trajectory scenes: n_alphas out of range";
+  const DIlqr<real> d = make_ilqr<real>(*cf);
+  if (d.nc != FK_NS::NC || cf->n_alphas - d.nc > 1)
+    return "per-trajectory scenes: six non-zero line-search alphas (plus at most one zero)";
+  const char* e = getenv("DTMPC_FAST");
+  if (e && e[0] == '0' && e[1] == 0) return "per-trajectory scenes: the fused kernels are switched off (DTMPC_FAST=0)";
+  return nullptr;
+}
+
+#define SC_M(m) (m | FK_NS::kScene)
+int launch_tube_fast_scenes(int M, int lanes, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FK& kk) {
+#define SC_LAUNCH(m, l) hipLaunchKernelGGL((FK_NS::tube_fast_kernel<SC_M(m), l, 2>), grid, dim3(bs), 0, st, kk)
+#define SC_CASE(m) \
+  case m:          \
+    if (lanes == 4) SC_LAUNCH(m, 4); else if (lanes == 2) SC_LAUNCH(m, 2); else SC_LAUNCH(m, 1); \
+    return 0;
+  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "scenes tube unit: lanes");
+  switch (M) {
+#ifdef DTMPC_FAST_M_ONLY
+    SC_CASE(DTMPC_FAST_M_ONLY)
+#else
+    SC_CASE(1) SC_CASE(2) SC_CASE(3) SC_CASE(4) SC_CASE(5) SC_CASE(6) SC_CASE(7) SC_CASE(8)
+#endif
+    default: return set_err(DTMPC_ERR_BAD_ARG, "fast tube step with scenes: obstacle count not instantiated");
+  }
+#undef SC_CASE
+#undef SC_LAUNCH
+}
+
+int launch_ilqr_fast_scenes(int M, int lanes, bool track, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::IK& kk) {
+#define SC_LAUNCH(m, l, t) hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<SC_M(m), l, t, 2>), grid, dim3(bs), 0, st, kk)
+#define SC_T(m, l) \
+  if (track) SC_LAUNCH(m, l, true); else SC_LAUNCH(m, l, false);
+#define SC_CASE(m) \
+  case m:          \
+    if (lanes == 4) { SC_T(m, 4) } else if (lanes == 2) { SC_T(m, 2) } else { SC_T(m, 1) } \
+    return 0;
+  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "scenes iLQR unit: lanes");
+  switch (M) {
+#ifdef DTMPC_FAST_M_ONLY
+    SC_CASE(DTMPC_FAST_M_ONLY)
+#else
+    SC_CASE(1) SC_CASE(2) SC_CASE(3) SC_CASE(4) SC_CASE(5) SC_CASE(6) SC_CASE(7) SC_CASE(8)
+#endif
+    default: return set_err(DTMPC_ERR_BAD_ARG, "fast iLQR with scenes: obstacle count not instantiated");
+  }
+#undef SC_CASE
+#undef SC_T
+#undef SC_LAUNCH
+}
+#undef SC_M
 
 #else  // the general path's solves (csrc/dtmpc_fast_general.hip)
 

@@ -33,6 +33,22 @@ __global__ void __launch_bounds__(kBlock) dbas_init_kernel(DSpec<T> s, int B, co
   b[i] = barrier_of_state(s, x[i], x[(size_t)B + i]);
 }
 
+// b0 = B(h(x0)) with each trajectory's own obstacles: rows cx[0..M), cy[0..M), r2[0..M) of the scenes array
+// [3M + 3][B] (include/dtmpc.h) replace the spec's table, then the shared kernel's evaluation
+template <typename T>
+__global__ void __launch_bounds__(kBlock) dbas_init_scenes_kernel(DSpec<T> s, int B, const T* x, const T* scenes, T* b) {
+  int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B) return;
+  const size_t nb = (size_t)B;
+  const T* q = scenes + i;
+  for (int j = 0; j < s.M; ++j) {
+    s.cx[j] = q[(size_t)j * nb];
+    s.cy[j] = q[(size_t)(s.M + j) * nb];
+    s.r2[j] = q[(size_t)(2 * s.M + j) * nb];
+  }
+  b[i] = barrier_of_state(s, x[i], x[nb + i]);
+}
+
 // episode start of the fused closed loop in one launch (core/tube_mpc.py:770-779): x = xbar = x0 (given
 // trajectory-major [B][3], the reference's layout), b = bbar = B(h(x0)), zero warm starts (both
 // [N][2][B] tapes: each lane clears its own column), status 0; lane 0 restores theta and clears the
@@ -608,6 +624,28 @@ int dtmpc_dbas_init(int dtype, const dtmpc_spec* spec, int64_t B, const void* x,
   return check_launch("dbas_init_kernel");
 }
 
+int dtmpc_dbas_init_scenes(int dtype, const dtmpc_spec* spec, int64_t B, const void* x, const void* scenes, void* b,
+                           void* stream) {
+  int e = check_spec(spec, B);
+  if (e) return e;
+  if (!x || !b || !scenes) return set_err(DTMPC_ERR_BAD_ARG, "NULL array");
+  if (spec->n_obstacles < 1 || spec->obs_aggregation == DTMPC_OBS_NONE)
+    return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes need at least one obstacle");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DTMPC_F32)
+    hipLaunchKernelGGL(dbas_init_scenes_kernel<float>, grid_for(B), dim3(kBlock), 0, st, make_spec<float>(*spec), (int)B, (const float*)x, (const float*)scenes, (float*)b);
+  else if (dtype == DTMPC_F64)
+    hipLaunchKernelGGL(dbas_init_scenes_kernel<double>, grid_for(B), dim3(kBlock), 0, st, make_spec<double>(*spec), (int)B, (const double*)x, (const double*)scenes, (double*)b);
+  else
+    return set_err(DTMPC_ERR_BAD_ARG, "bad dtype");
+  return check_launch("dbas_init_scenes_kernel");
+}
+
+int32_t dtmpc_scenes_supported(int dtype, const dtmpc_spec* spec, const dtmpc_ilqr_cfg* cfg) {
+  if (!spec || !cfg) return 0;
+  return scenes_unsupported(dtype, spec, cfg) ? 0 : 1;
+}
+
 int dtmpc_tube_reset(int dtype, const dtmpc_spec* spec, int64_t B, const void* x0, const dtmpc_tube_state* S,
                      const void* theta0, void* theta, void* vel, void* stream) {
   int e = check_spec(spec, B);
@@ -627,7 +665,12 @@ int dtmpc_tube_reset(int dtype, const dtmpc_spec* spec, int64_t B, const void* x
   else
     return set_err(DTMPC_ERR_BAD_ARG, "bad dtype");
 #undef RESET
-  return check_launch("tube_reset_kernel");
+  if ((e = check_launch("tube_reset_kernel"))) return e;
+  if (S->scenes) {  // b = bbar = B(h(x0)) with each trajectory's own obstacles (x = xbar = x0 are in place)
+    if ((e = dtmpc_dbas_init_scenes(dtype, spec, B, S->x, S->scenes, S->b, stream))) return e;
+    return dtmpc_dbas_init_scenes(dtype, spec, B, S->xbar, S->scenes, S->bbar, stream);
+  }
+  return DTMPC_OK;
 }
 
 int dtmpc_linearize(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
@@ -696,6 +739,29 @@ int dtmpc_ilqr_solve_ws(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cos
     return launch_ilqr_fast64(spec, cost, cfg, B, x0, Xref, Uref, X, U, K, kff, iters, status, (signed char*)choices,
                               costs, lanes, work, work_bytes, (hipStream_t)stream);
   return dtmpc_ilqr_solve(dtype, spec, cost, cfg, B, x0, Xref, Uref, X, U, K, kff, iters, status, choices, stream);
+}
+
+int dtmpc_ilqr_solve_scenes(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost,
+                            const dtmpc_ilqr_cfg* cfg, int64_t B, const void* x0, const void* Xref,
+                            const void* Uref, void* X, void* U, void* K, void* kff, int32_t* iters,
+                            int32_t* status, int8_t* choices, void* costs, int32_t lanes, void* work,
+                            size_t work_bytes, const void* scenes, void* stream) {
+  if (!scenes)
+    return dtmpc_ilqr_solve_ws(dtype, spec, cost, cfg, B, x0, Xref, Uref, X, U, K, kff, iters, status, choices, costs,
+                               lanes, work, work_bytes, stream);
+  int e = check_spec(spec, B);
+  if (e) return e;
+  if ((e = check_cost(cost, Xref, Uref))) return e;
+  if ((e = check_ilqr(cfg))) return e;
+  if (!x0 || !X || !U || !K || !kff || !status) return set_err(DTMPC_ERR_BAD_ARG, "NULL array");
+  if (lanes == 0) lanes = tube_lanes_default(B, dtype);
+  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "lanes must be 0, 1, 2 or 4");
+  // never the shared table in place of the scenes: an unsupported configuration is an error
+  if (const char* why = scenes_unsupported(dtype, spec, cfg)) return set_err(DTMPC_ERR_BAD_ARG, why);
+  if (!ilqr_fast_eligible(dtype, spec, cost, cfg))
+    return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes: the cost must not wrap the heading error");
+  return launch_ilqr_fast(spec, cost, cfg, B, x0, Xref, Uref, X, U, K, kff, iters, status, (signed char*)choices, costs,
+                          lanes, work, work_bytes, (hipStream_t)stream, scenes);
 }
 
 size_t dtmpc_sensitivity_workspace_bytes(int dtype, int32_t horizon, int64_t B, int32_t want_lambda) {
@@ -822,6 +888,13 @@ int dtmpc_tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg
     return set_err(DTMPC_ERR_BAD_ARG, "a split step (state->phase 1 / 2) needs the fused kernel and B within one launch "
                                       "chunk of the precision (dtmpc_tube_split_ok)");
   hipStream_t st = (hipStream_t)stream;
+  if (S->scenes) {  // never the shared table in place of the scenes: an unsupported configuration is an error
+    const char* why = scenes_unsupported(dtype, spec, &cfg->nom_ilqr);
+    if (!why) why = scenes_unsupported(dtype, spec, &cfg->aux_ilqr);
+    if (why) return set_err(DTMPC_ERR_BAD_ARG, why);
+    if (!tube_fast_eligible(dtype, spec, cfg))
+      return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes: the nominal cost must not wrap the heading error");
+  }
   if (tube_fast_eligible(dtype, spec, cfg)) return launch_tube_fast(spec, cfg, B, global_offset, step, S, w, st);
   if (tube_fast_eligible64(dtype, spec, cfg))
     return launch_tube_fast64(spec, cfg, B, global_offset, step, S, w, st);

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_OBS = 16
 MAX_ALPHAS = 8
 MAX_HORIZON = 512
@@ -121,6 +121,7 @@ class DtmpcTubeState(C.Structure):
         ("work_bytes", C.c_int64),
         ("choices", C.c_void_p),
         ("costs", C.c_void_p),
+        ("scenes", C.c_void_p),
     ]
 
 
@@ -197,6 +198,13 @@ PROTOTYPES = {
         [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), C.POINTER(DtmpcIlqrCfg), I64, P, P, P, P, P, P, P, P, P, P,
          P, I32, P, C.c_size_t, P],
     ),
+    "dtmpc_scenes_supported": (I32, [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcIlqrCfg)]),
+    "dtmpc_ilqr_solve_scenes": (
+        C.c_int,
+        [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), C.POINTER(DtmpcIlqrCfg), I64, P, P, P, P, P, P, P, P, P, P,
+         P, I32, P, C.c_size_t, P, P],
+    ),
+    "dtmpc_dbas_init_scenes": (C.c_int, [C.c_int, C.POINTER(DtmpcSpec), I64, P, P, P, P]),
     "dtmpc_sensitivity_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64, I32]),
     "dtmpc_ddp_sensitivity": (
         C.c_int,

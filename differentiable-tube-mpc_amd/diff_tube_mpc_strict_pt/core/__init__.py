@@ -26,6 +26,7 @@ from .problem import (
     PaperSetup,
     QuadraticCost,
     general_setup_from_config,
+    pack_scenes,
     paper_setup_from_config,
     problem_from_config,
     tracking_cost,
@@ -74,6 +75,7 @@ __all__ = [
     "doc_gradient",
     "ilqr_solve",
     "linearize",
+    "pack_scenes",
     "paper_setup_from_config",
     "problem_from_config",
     "raise_for_status",

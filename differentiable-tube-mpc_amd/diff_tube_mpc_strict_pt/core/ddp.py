@@ -28,7 +28,7 @@ import torch
 from torch import Tensor
 
 from .. import _abi, _lib
-from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost
+from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes
 
 __all__ = [
     "ILQRConfig",
@@ -147,14 +147,20 @@ def rollout(problem, x0: Tensor, V: Optional[Tensor] = None, *, f=None) -> Tenso
     return from_soa(Xs)
 
 
-def dbas_init(problem: DubinsDBaSProblem, x: Tensor) -> Tensor:
-    """b0 = B(h(x0)) per trajectory (core/barrier.py:111-120).  x: [B, 3] -> [B]."""
-    _require_device(x)
+def dbas_init(problem: DubinsDBaSProblem, x: Tensor, scenes: Optional[Tensor] = None) -> Tensor:
+    """b0 = B(h(x0)) per trajectory (core/barrier.py:111-120).  x: [B, 3] -> [B].
+    scenes ([3M + 3, B], problem.pack_scenes): each trajectory's own obstacles instead of the problem's."""
+    _require_device(x, scenes)
     B = x.shape[0]
     lib = _lib.load()
     spec = problem.to_c()
     xs = x[:, :3].t().contiguous()
     b = torch.empty(B, dtype=x.dtype, device=x.device)
+    if scenes is not None:
+        check_scenes(scenes, len(problem.obstacles), B, x.dtype, x.device)
+        _lib.check(lib.dtmpc_dbas_init_scenes(_dtype_code(x), C.byref(spec), B, xs.data_ptr(), scenes.data_ptr(),
+                                              b.data_ptr(), _lib.stream_of(x)), "dtmpc_dbas_init_scenes")
+        return b
     _lib.check(lib.dtmpc_dbas_init(_dtype_code(x), C.byref(spec), B, xs.data_ptr(), b.data_ptr(),
                                    _lib.stream_of(x)), "dtmpc_dbas_init")
     return b
@@ -185,6 +191,7 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
                cfg: ILQRConfig, x0: Tensor, V_init: Tensor, X_ref: Optional[Tensor] = None,
                U_ref: Optional[Tensor] = None, check: bool = True, debug_name: str = "ilqr",
                record_choices: bool = False, lanes: int = 0, record_costs: bool = False,
+               scenes: Optional[Tensor] = None,
                f=None, f_jac=None, ctrl=None, stage_cost=None, terminal_cost=None, stage_derivs=None,
                terminal_derivs=None, feasible_fn=None, debug: bool = False):
     """Batched box-clamped iLQR (core/ddp.py:102-307).
@@ -201,8 +208,13 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
     Runs dtmpc_ilqr_solve_ws: the tube step's fused solver on the paper configuration (f32 and f64:
     csrc/dtmpc_fast_ilqr.hip / dtmpc_fast64_ilqr.hip; DTMPC_FAST=0 / DTMPC_FAST64=0 switch it off) with
     ``lanes`` lanes per trajectory (0: dtmpc_tube_lanes(B); 1, 2 or 4), else the generic kernel
-    (dtmpc_ilqr_fused_eligible says which)."""
+    (dtmpc_ilqr_fused_eligible says which).
+    scenes ([3M + 3, B], problem.pack_scenes): trajectory i solves with its own obstacles and -- for the target
+    cost -- its own target (``cost.target`` is then unused); fused f32 solver only, ValueError where
+    dtmpc_scenes_supported says no."""
     if f is not None:
+        if scenes is not None:
+            raise TypeError("scenes go with the typed form (problem / cost)")
         if problem is not None or cost is not None:
             raise TypeError("pass either problem / cost (typed form) or the closures (keyword form), not both")
         from .closures import resolve_ilqr
@@ -245,12 +257,25 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
         raise ValueError("lanes must be 0 (default), 1, 2 or 4")
     wb = int(lib.dtmpc_ilqr_workspace_bytes(_dtype_code(x0), N, B, lanes))
     work = torch.empty(max(wb, 1), dtype=torch.uint8, device=x0.device)
-    _lib.check(lib.dtmpc_ilqr_solve_ws(_dtype_code(x0), C.byref(spec), C.byref(cc), C.byref(ic), B, x0s.data_ptr(),
-                                       _ptr(Xr), _ptr(Ur), Xs.data_ptr(), Us.data_ptr(), Ks.data_ptr(), ks.data_ptr(),
-                                       iters.data_ptr(), status.data_ptr(), _ptr(ch), _ptr(cr), lanes,
-                                       work.data_ptr(), wb,
-                                       _lib.stream_of(x0)),
-               "dtmpc_ilqr_solve_ws")
+    if scenes is not None:
+        _require_device(scenes)
+        check_scenes(scenes, len(problem.obstacles), B, dt, x0.device)
+        if not lib.dtmpc_scenes_supported(_dtype_code(x0), C.byref(spec), C.byref(ic)) or cost.wrap_angle:
+            raise ValueError("per-trajectory scenes are not supported for this dtype / problem / line search "
+                             "(dtmpc_scenes_supported: f32, smooth-min, 1..8 obstacles, inverse barrier, gamma = 0, "
+                             "six non-zero alphas, no wrapped heading error)")
+        _lib.check(lib.dtmpc_ilqr_solve_scenes(_dtype_code(x0), C.byref(spec), C.byref(cc), C.byref(ic), B,
+                                               x0s.data_ptr(), _ptr(Xr), _ptr(Ur), Xs.data_ptr(), Us.data_ptr(),
+                                               Ks.data_ptr(), ks.data_ptr(), iters.data_ptr(), status.data_ptr(),
+                                               _ptr(ch), _ptr(cr), lanes, work.data_ptr(), wb, scenes.data_ptr(),
+                                               _lib.stream_of(x0)),
+                   "dtmpc_ilqr_solve_scenes")
+    else:
+        _lib.check(lib.dtmpc_ilqr_solve_ws(_dtype_code(x0), C.byref(spec), C.byref(cc), C.byref(ic), B, x0s.data_ptr(),
+                                           _ptr(Xr), _ptr(Ur), Xs.data_ptr(), Us.data_ptr(), Ks.data_ptr(),
+                                           ks.data_ptr(), iters.data_ptr(), status.data_ptr(), _ptr(ch), _ptr(cr),
+                                           lanes, work.data_ptr(), wb, _lib.stream_of(x0)),
+                   "dtmpc_ilqr_solve_ws")
     if check:
         raise_for_status(status, debug_name)
     return ILQRResult(X=from_soa(Xs), V=from_soa(Us), K=from_soa(Ks).view(B, N, 2, 4), k=from_soa(ks),

@@ -266,6 +266,60 @@ def paper_config() -> Dict[str, Any]:
     }
 
 
+def pack_scenes(problem: DubinsDBaSProblem, obstacles, targets, dtype=None, device=None):
+    """Per-trajectory scenes for ``TubeMPC(scenes=)``, ``ilqr_solve(scenes=)`` and ``dbas_init(scenes=)``.
+
+    obstacles [B, M, 3]: each trajectory's circles (cx, cy, r), M = len(problem.obstacles); targets [B, 3]: its
+    nominal target (x, y, heading).  Returns the [3M + 3, B] tensor of include/dtmpc.h ("per-trajectory scenes"):
+    rows cx[0..M), cy[0..M), r2[0..M), then the target -- r2 the SQUARED radius, the product formed in float64 and
+    then rounded to ``dtype``, exactly as the library forms a spec's table, so a scene equal to the problem's own
+    obstacles gives bitwise the shared path's results.  Everything else (M, aggregation, beta, barrier, control box,
+    dt, weights) stays the problem's.  A scene with fewer obstacles: pad it with a circle far from the workspace
+    (under smooth-min its weight underflows to zero)."""
+    import torch
+
+    dtype = torch.float32 if dtype is None else dtype
+    def f64(a):  # a float64 host copy (a copy: the caller's array may be a read-only view)
+        if isinstance(a, torch.Tensor):
+            return a.detach().to(device="cpu", dtype=torch.float64)
+        import numpy as np
+
+        return torch.from_numpy(np.array(a, dtype=np.float64))
+
+    obs, tg = f64(obstacles), f64(targets)
+    M = len(problem.obstacles)
+    if M < 1:
+        raise ValueError("per-trajectory scenes need a problem with at least one obstacle")
+    if obs.dim() != 3 or obs.shape[2] != 3:
+        raise ValueError("obstacles must be [B, M, 3] (cx, cy, r)")
+    if obs.shape[1] != M:
+        raise ValueError(f"obstacles has {obs.shape[1]} circles per scene, the problem {M}")
+    B = obs.shape[0]
+    if tg.shape != (B, 3):
+        raise ValueError(f"targets must be [{B}, 3]")
+    if B < 1:
+        raise ValueError("empty batch")
+    if not bool((obs[:, :, 2] > 0).all()):
+        raise ValueError("obstacle radii must be positive")
+    if not bool(torch.isfinite(obs).all() and torch.isfinite(tg).all()):
+        raise ValueError("scenes must be finite")
+    r2 = obs[:, :, 2] * obs[:, :, 2]  # float64 product, rounded to dtype below (csrc/dtmpc_host.hpp make_spec)
+    rows = torch.cat([obs[:, :, 0].t(), obs[:, :, 1].t(), r2.t(), tg.t()], 0)  # [3M + 3, B]
+    return rows.to(dtype).contiguous().to(device=device)
+
+
+def check_scenes(scenes, M: int, B: int, dtype, device) -> None:
+    """The shape / dtype / placement contract of a packed scenes tensor (the kernels index it unchecked)."""
+    if scenes.dim() != 2 or tuple(scenes.shape) != (3 * M + 3, B):
+        raise ValueError(f"scenes must be [{3 * M + 3}, {B}] (pack_scenes), got {tuple(scenes.shape)}")
+    if scenes.dtype != dtype:
+        raise ValueError(f"scenes must be {dtype}, got {scenes.dtype}")
+    if scenes.device.type != device.type or (device.index is not None and scenes.device.index != device.index):
+        raise ValueError(f"scenes must live on {device}, got {scenes.device}")
+    if not scenes.is_contiguous():
+        raise ValueError("scenes must be contiguous")
+
+
 def tracking_cost(theta: Sequence[float]) -> QuadraticCost:
     """Ancillary tracking cost with weights theta = (Qa, Ra, qba); terminal weight Qa
     (core/tube_mpc.py:875-894)."""

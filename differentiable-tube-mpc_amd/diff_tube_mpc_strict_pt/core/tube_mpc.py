@@ -30,7 +30,8 @@ from torch import Tensor
 
 from .. import _abi, _lib
 from .ddp import _dtype_code, raise_for_status
-from .problem import GeneralSetup, PaperSetup, general_setup_from_config, paper_setup_from_config, softplus
+from .problem import (GeneralSetup, PaperSetup, check_scenes, general_setup_from_config, paper_setup_from_config,
+                      softplus)
 
 __all__ = ["ExperimentTrajectories", "TubeMPC", "GeneralTubeMPC", "run_closed_loop_experiment", "shard_range",
            "allreduce_sums", "DEFAULT_GRAD_BOUND_F32"]
@@ -101,12 +102,15 @@ class TubeMPC:
         f32 (the reference's own f32 path overflows on such trajectories: obstacle-grazing ancillary plans
         give |g| ~ 1e15-1e30 against ~1e2 typical), none in f64.  At B = 1 on the reference's closed loop
         the bound never triggers, so the update is the reference's exactly (tests/test_gpu_parity.py).
+      scenes: per-trajectory obstacles and nominal target ([3M + 3, batch], problem.pack_scenes; a shard passes
+        its own columns of the global array) or None: every trajectory runs the setup's problem.  Fused f32
+        kernels only (dtmpc_scenes_supported); see :meth:`set_scenes`.
     """
 
     def __init__(self, setup, *, batch: int, device="cuda", dtype=torch.float32, disturbance: str = "philox",
                  seed: int = 0, global_offset: int = 0, global_batch: Optional[int] = None, process_group=None,
                  write_log: bool = False, record_choices: bool = False, grad_bound: Optional[float] = None,
-                 record_costs: bool = False, overlap: Optional[bool] = None):
+                 record_costs: bool = False, overlap: Optional[bool] = None, scenes: Optional[Tensor] = None):
         if isinstance(setup, dict):
             setup = paper_setup_from_config(setup)
         self.setup: PaperSetup = setup
@@ -196,7 +200,9 @@ class TubeMPC:
         st.choices = self.choices.data_ptr() if self.choices is not None else None
         st.costs = self.costs.data_ptr() if self.costs is not None else None
         st.phase = 0
+        st.scenes = None
         self.state = st
+        self.scenes: Optional[Tensor] = None
         # overlap (the nominal solve is theta-independent, core/tube_mpc.py:723-728): each step runs
         # as two launches (dtmpc_tube_state.phase 1: nominal, 2: the rest) and its theta all-reduce + update go to
         # a side stream, which the NEXT step's phase 2 waits on -- so the collective overlaps the next nominal
@@ -212,6 +218,27 @@ class TubeMPC:
             raise ValueError("overlap needs the fused tube kernel and B within one launch chunk (dtmpc_tube_split_ok)")
         self.overlap = bool(can and (multi if overlap is None else overlap))
         self._side = torch.cuda.Stream(device=self.device) if self.overlap else None
+        if scenes is not None:
+            self.set_scenes(scenes)
+
+    def set_scenes(self, scenes: Optional[Tensor]) -> None:
+        """Change the per-trajectory scenes ([3M + 3, batch], problem.pack_scenes; None: back to the setup's shared
+        problem) between episodes: call it BEFORE :meth:`reset`, which forms b0 from the new obstacles.  The tensor
+        is kept (not copied) and read by every later launch."""
+        self.join()  # like the other setters: the side stream's theta update is done before the state changes
+        if scenes is None:
+            self.scenes, self.state.scenes = None, None
+            return
+        check_scenes(scenes, len(self.setup.problem.obstacles), self.B, self.dtype, self.device)
+        for ic in (self.cfg.nom_ilqr, self.cfg.aux_ilqr):
+            if not self.lib.dtmpc_scenes_supported(self._dt, C.byref(self.spec), C.byref(ic)):
+                raise ValueError("per-trajectory scenes are not supported for this dtype / problem / line search "
+                                 "(dtmpc_scenes_supported: f32, smooth-min, 1..8 obstacles, inverse barrier, "
+                                 "gamma = 0, six non-zero alphas)")
+        if self.cfg.nominal.wrap_angle:
+            raise ValueError("per-trajectory scenes: the nominal cost must not wrap the heading error")
+        self.scenes = scenes
+        self.state.scenes = scenes.data_ptr()
 
     # -----------------------------------------------------------------------------------------
     def join(self) -> None:
@@ -258,8 +285,13 @@ class TubeMPC:
         xs = x0.to(device=self.device, dtype=self.dtype).t().contiguous()
         self.x.copy_(xs)
         self.xbar.copy_(xs)
-        _lib.check(self.lib.dtmpc_dbas_init(self._dt, C.byref(self.spec), self.B, self.x.data_ptr(),
-                                            self.b.data_ptr(), self._stream()), "dtmpc_dbas_init")
+        if self.scenes is not None:
+            _lib.check(self.lib.dtmpc_dbas_init_scenes(self._dt, C.byref(self.spec), self.B, self.x.data_ptr(),
+                                                       self.scenes.data_ptr(), self.b.data_ptr(), self._stream()),
+                       "dtmpc_dbas_init_scenes")
+        else:
+            _lib.check(self.lib.dtmpc_dbas_init(self._dt, C.byref(self.spec), self.B, self.x.data_ptr(),
+                                                self.b.data_ptr(), self._stream()), "dtmpc_dbas_init")
         self.bbar.copy_(self.b)
         self.Unom.zero_()
         self.Uaux.zero_()

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DTMPC_ABI_VERSION 7
+#define DTMPC_ABI_VERSION 8
 #define DTMPC_MAX_OBS 16
 #define DTMPC_MAX_ALPHAS 8
 #define DTMPC_MAX_HORIZON 512
@@ -194,6 +194,10 @@ typedef struct dtmpc_tube_state {
                        candidates that ran are written (pre-fill it, e.g. with NaN).  Written by the fused
                        kernels only (diagnostics / the tie-aware parity
                        gate, tests/_common.py); the generic kernel leaves it untouched */
+  const void* scenes; /* ABI 8: [3M + 3][B] (dtype) per-trajectory scenes, or NULL: every trajectory runs the spec's
+                       obstacle table and cfg->nominal.target (the behaviour up to ABI 7).  Layout below
+                       ("per-trajectory scenes"); honoured by dtmpc_tube_step and dtmpc_tube_reset where
+                       dtmpc_scenes_supported, DTMPC_ERR_BAD_ARG elsewhere */
 } dtmpc_tube_state;
 
 int dtmpc_abi_version(void);
@@ -268,6 +272,44 @@ int dtmpc_ilqr_solve_ws(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cos
                         const void* Xref, const void* Uref, void* X, void* U,
                         void* K, void* kff, int32_t* iters, int32_t* status, int8_t* choices,
                         void* costs, int32_t lanes, void* work, size_t work_bytes, void* stream);
+
+/* ---- per-trajectory scenes (ABI 8) ------------------------------------------------------- */
+/*
+ * A scene is ONE trajectory's environment: its M circle obstacles and its nominal target.  M, the
+ * aggregation, beta, the barrier, the control box, dt and every weight stay the spec's and the cost's,
+ * shared by the batch.  `scenes` is SoA [3M + 3][B] in the batch dtype, M = spec->n_obstacles:
+ *   rows 0 .. M-1     obstacle centre x        rows M .. 2M-1   obstacle centre y
+ *   rows 2M .. 3M-1   SQUARED radius, formed as the library forms it from a spec: the product in double,
+ *                     then rounded to the dtype -- so a scene equal to the spec's table gives bitwise the
+ *                     shared path's results
+ *   rows 3M .. 3M+2   nominal target x, y, heading (read by a DTMPC_COST_TARGET cost; a tracking cost
+ *                     ignores them, but the rows are part of the layout)
+ * Element (row, i) at index row * B + i; a shard of a global batch passes its own columns.  A per-trajectory
+ * obstacle COUNT is not supported: pad a scene with an obstacle far from the workspace (under smooth-min
+ * its weight exp(-beta (h_far - h_min)) underflows to zero).
+ * The fused f32 kernels read a lane's scene into registers at each phase start (csrc/dtmpc_fast_scenes.hip);
+ * there is no generic-kernel or f64 form: a scenes pointer on a configuration dtmpc_scenes_supported
+ * rejects returns DTMPC_ERR_BAD_ARG, never the shared table. */
+
+/* 1 when `scenes` is honoured for this precision / problem / line search: DTMPC_F32, smooth-min aggregation,
+ * 1 <= M <= 8, relaxed inverse barrier, dbas_gamma == 0, h_offset == 0, six non-zero line-search alphas
+ * (plus at most one alpha = 0), and DTMPC_FAST not 0 in the environment; else 0.  Host-only. */
+int32_t dtmpc_scenes_supported(int dtype, const dtmpc_spec* spec, const dtmpc_ilqr_cfg* cfg);
+
+/* dtmpc_ilqr_solve_ws with per-trajectory scenes: trajectory i solves with the obstacles of column i and,
+ * for DTMPC_COST_TARGET, the target of column i (cost->target is then unused).  scenes == NULL is
+ * dtmpc_ilqr_solve_ws.  DTMPC_ERR_BAD_ARG where dtmpc_scenes_supported is 0 or the cost wraps the heading. */
+int dtmpc_ilqr_solve_scenes(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost,
+                            const dtmpc_ilqr_cfg* cfg, int64_t B, const void* x0,
+                            const void* Xref, const void* Uref, void* X, void* U,
+                            void* K, void* kff, int32_t* iters, int32_t* status, int8_t* choices,
+                            void* costs, int32_t lanes, void* work, size_t work_bytes,
+                            const void* scenes, void* stream);
+
+/* dtmpc_dbas_init with per-trajectory scenes: b0 = B(h(x0)) with trajectory i's own obstacles (f32 and f64,
+ * every aggregation with at least one obstacle).  dtmpc_tube_reset uses it when the state carries scenes. */
+int dtmpc_dbas_init_scenes(int dtype, const dtmpc_spec* spec, int64_t B, const void* x, const void* scenes,
+                           void* b, void* stream);
 
 /* Scratch bytes for dtmpc_ddp_sensitivity. */
 size_t dtmpc_sensitivity_workspace_bytes(int dtype, int32_t horizon, int64_t B, int32_t want_lambda);
