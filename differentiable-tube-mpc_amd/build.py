@@ -3,7 +3,8 @@
 Plain hipcc, no build system: the translation units compiled in parallel, then linked --
 csrc/dtmpc_kernels.hip (paper path + per-function entry points), csrc/dtmpc_fast.hip (the fused tube step of
 the paper configuration), csrc/dtmpc_fast_ilqr.hip (its solver as the standalone batched iLQR), csrc/dtmpc_fast_general.hip (the
-general path's solves on it), csrc/dtmpc_fast_scenes.hip (both with per-trajectory scenes), csrc/dtmpc_general.hip (general IFT
+general path's solves on it), csrc/dtmpc_fast_scenes.hip (both with per-trajectory scenes), csrc/dtmpc_fast_own.hip (the tube step with
+per-trajectory ancillary weights), csrc/dtmpc_general.hip (general IFT
 path), csrc/dtmpc_receding.hip (receding-horizon nominal MPC driver), csrc/dtmpc_control.hip (tanh-box
 control map + cost derivatives), csrc/dtmpc_ocp.hip (tape cost of core/ocp.py), csrc/dtmpc_systems.hip
 (per-point kernels of the reference's per-function API: dynamics, h, barriers, Jacobians, clamp, cost
@@ -20,7 +21,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", f)
         for f in ("dtmpc_kernels.hip", "dtmpc_fast.hip", "dtmpc_fast_ilp.hip", "dtmpc_fast64.hip", "dtmpc_fast64_ilp.hip",
-                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
+                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
                   "dtmpc_control.hip", "dtmpc_ocp.hip", "dtmpc_systems.hip")]
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("dtmpc_device.hpp", "dtmpc_solver.hpp", "dtmpc_general.hpp",
                                                  "dtmpc_host.hpp", "dtmpc_ls_pk.hpp")] + [
@@ -37,10 +38,10 @@ FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno-
 # and the f32 standalone-iLQR / receding unit (config 2 -1.3 %, receding -0.8 %; its f64 twin lost 1.2 % and keeps the
 # default) and the f32 general-path unit (general IFT step -1.1 %); the per-trajectory-scenes unit follows its
 # shared twins: the one- and two-lane tube kernels and every standalone-iLQR form are built with it there (its
-# four-lane tube kernels ride along, not measured apart)
+# four-lane tube kernels ride along, not measured apart), and the own-theta unit follows the scenes unit
 UNIT_FLAGS = {u: ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
               for u in ("dtmpc_fast_ilp", "dtmpc_fast64_ilp", "dtmpc_fast_ilqr", "dtmpc_fast_general",
-                        "dtmpc_fast_scenes")}
+                        "dtmpc_fast_scenes", "dtmpc_fast_own")}
 
 
 def _lib_key() -> str:
@@ -132,13 +133,16 @@ def build(force: bool = False, variant: str = "", defines=(), only=(), on_produc
                                ", ".join(f"{k} ({b} B)" for k, b in bad))
         # and no 128-bit record store of a fused kernel may have its data registers written inside its two wait
         # states (the store-data hazard, csrc/dtmpc_fast.hip st128; profiles/r05/store_hazard.txt)
+        # (one disassembly per unit, the units scanned side by side: the scans are single-threaded text passes over
+        # millions of instructions and, run one after the other, took longer than compiling did)
+        from concurrent.futures import ProcessPoolExecutor
+
         haz, vh, fc = {}, {}, {}
-        for o in objs:
-            tu = os.path.basename(o).split(".")[0]
-            if tu.startswith("dtmpc_fast"):
-                haz[tu] = [list(h) for h in store_hazards(o)]
-                vh[tu] = [list(h) for h in valu_hazards(o)]
-            fc[tu] = [list(h) for h in flow_copies(o)]  # every unit: the generic kernels branch per lane as well
+        with ProcessPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+            for tu, h, v, f in pool.map(_scan_unit, objs):
+                if h is not None:
+                    haz[tu], vh[tu] = h, v
+                fc[tu] = f  # every unit: the generic kernels branch per lane as well
         with open(os.path.join(CACHE, "flow_copies.json"), "w") as f:
             json.dump(fc, f, indent=1, sort_keys=True)
         nf = sum(len(v) for v in fc.values())
@@ -207,6 +211,21 @@ def _code_object(obj: str, d: str) -> str:
     subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
                     f"--targets=hipv4-amdgcn-amd-amdhsa--{ARCH}", f"--output={co}"], check=True, capture_output=True)
     return co
+
+
+def _scan_unit(obj: str):
+    """(unit, store hazards, VALU hazards, flow copies) of one object from ONE disassembly: what store_hazards,
+    valu_hazards and flow_copies return, as lists; the first two only for the fused units (None elsewhere)."""
+    import tempfile
+
+    tu = os.path.basename(obj).split(".")[0]
+    with tempfile.TemporaryDirectory() as d:
+        co = _code_object(obj, d)
+        dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", f"--mcpu={ARCH}", "--no-show-raw-insn",
+                              "--no-leading-addr", co], check=True, capture_output=True, text=True).stdout
+    fused = tu.startswith("dtmpc_fast")
+    return (tu, [list(h) for h in scan_store_hazards(dis)] if fused else None,
+            [list(h) for h in scan_valu_hazards(dis)] if fused else None, [list(h) for h in scan_flow_copies(dis)])
 
 
 def _vregs(tok: str):

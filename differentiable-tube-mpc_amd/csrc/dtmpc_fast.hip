@@ -21,6 +21,8 @@
 // (sensitivity), core/tube_mpc.py:915-984 (upper loss, DOC gradient, update).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/dtmpc.h"
 #include "dtmpc_host.hpp"
 #include "dtmpc_ls_pk.hpp"
@@ -28,7 +30,7 @@
 // this file is the tube step's translation unit; dtmpc_fast_ilqr.hip / dtmpc_fast_general.hip include it
 // for the standalone iLQR's and the general path's instantiations (their host parts below)
 #if defined(DTMPC_FAST_ILQR_TU) || defined(DTMPC_FAST_GENERAL_TU) || defined(DTMPC_FAST_ILP_TU) || \
-    defined(DTMPC_FAST_SCENES_TU)
+    defined(DTMPC_FAST_SCENES_TU) || defined(DTMPC_FAST_OWN_TU)
 #define DTMPC_FAST_AUX_TU 1
 #endif
 // The one-lane tube kernels (the headline's form) and the f32 two-lane ones live in their own translation units
@@ -111,6 +113,12 @@ constexpr int kXasm = 128;
 // instead of the kernarg block's copy (scene_p below).  Everything after the phase start reads the same registers, so
 // the step loops are the shared form's; only csrc/dtmpc_fast_scenes.hip instantiates it.
 constexpr int kScene = 256;
+// kOwn (f32): per-trajectory ancillary weights ("own theta", dtmpc_tube_step_own) -- the ancillary phase fills its cost
+// from the trajectory's own column of theta [6][B] instead of the batch's shared [6], and after the health test the
+// trajectory's first lane applies theta_update_kernel's momentum + projected update to that column from its own
+// gradient row (own_update below).  The step loops are the shared form's with the six weights in per-lane registers;
+// only csrc/dtmpc_fast_own.hip instantiates it.
+constexpr int kOwn = 512;
 template <int M>
 struct Obs {
   static constexpr int n = M & (kTight - 1);
@@ -119,6 +127,7 @@ struct Obs {
   static constexpr bool reread = (M & kReread) != 0;
   static constexpr bool xasm = (M & kXasm) != 0;
   static constexpr bool scene = (M & kScene) != 0;
+  static constexpr bool own = (M & kOwn) != 0;
 };
 
 // obstacle i of the table: the registers of FP, or (kReread) loaded again at each use -- through an opaque pointer
@@ -2320,6 +2329,25 @@ struct FK {
   FIlqr cfn, cfa;
   FArgs a;
 };
+// The kOwn instantiations' argument block: FK first (kargs() reads it as every kernel does), then the own-theta
+// arguments (dtmpc_own_theta).  They are a block of their own, and not more fields of FArgs, because FK has 8 bytes of
+// tail padding left: anything longer grows every kernel's explicit arguments and moves the hidden ones behind them
+// (the workgroup size each kernel loads), i.e. changes an instruction of every shared instantiation.
+struct OwnArgs {
+  real* th;   // [6][B] in/out: trajectory i's ancillary weights, column i
+  real* vel;  // [6][B] in/out: its update's momentum
+  real mom, eta, qmin, rmin, qbmin, qbmax;  // dtmpc_adapt_cfg in the batch precision
+  int upd;    // 0: hold theta (the weights are still read per trajectory)
+};
+struct FKOwn {
+  FK k;
+  OwnArgs o;
+};
+// the kernel parameter of an instantiation with obstacle argument M
+template <int M>
+struct FKOf {
+  typedef typename std::conditional<(M & kOwn) != 0, FKOwn, FK>::type type;
+};
 typedef const FK KArg;
 typedef __attribute__((address_space(4))) const FK KArg4;
 
@@ -2382,6 +2410,27 @@ __device__ __forceinline__ f4 scene_tg(const real* sc, size_t nb, int i) {
   const real* q = sc + i;
   return f4{q[(size_t)(3 * n) * nb], q[(size_t)(3 * n + 1) * nb], q[(size_t)(3 * n + 2) * nb], 0.f};
 }
+// kOwn: trajectory i's momentum + projected update of its own column of theta / vel [6][B] from its own gradient row
+// g (acc[1..6] after the health masking: zeros for a trajectory left out, whose momentum still decays and moves
+// theta -- the shared update at B = 1 with an empty healthy set).  The roundings are theta_update_kernel<float>'s as
+// compiled for gfx950: it forms momentum * vel in a packed multiply beside g = sums * inv_batch and ADDS them (two
+// roundings, no contraction), then theta - eta * vel as ONE fma(-eta, vel, theta); the projections are compares and
+// selects (a NaN stays).  Written out here, so that neither depends on where this kernel's compiler would fuse.
+// g + 0: the shared path's g went through the workgroup and batch sums, which turn a -0 into +0.
+__device__ __forceinline__ void own_update(const OwnArgs& a, size_t nb, int i, const real* g) {
+  DTMPC_NOCONTRACT
+  real* th = a.th + i;
+  real* ve = a.vel + i;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const real mv = a.mom * ve[(size_t)j * nb];
+    const real v = mv + (g[j] + real(0));
+    const real t = __builtin_elementwise_fma(-a.eta, v, th[(size_t)j * nb]);
+    ve[(size_t)j * nb] = v;
+    th[(size_t)j * nb] = j < 3 ? (t < a.qmin ? a.qmin : t) : j < 5 ? (t < a.rmin ? a.rmin : t) : clampv(t, a.qbmin, a.qbmax);
+  }
+}
+
 // the kScene phase start of trajectory i of the tube step.  (The kernels choose between this and phase_p<M>() by a
 // constant condition at the call, so that the shared instantiations compile from exactly the text they had: an extra
 // by-value hop of FP / FCost through a helper moved their register allocation.)
@@ -2427,7 +2476,7 @@ constexpr int tab_flag() {
 // One wave per SIMD at every lane count (amdgpu_waves_per_eu(1, 1)): the whole 512-register budget.
 template <int M, int P, int GM>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1)))
-tube_fast_kernel(FK kk) {
+tube_fast_kernel(typename FKOf<M>::type kk) {
   constexpr bool G0 = GM > 0, RG0 = GM > 1, SCC = GM > 2;
   constexpr int ML = M | tab_flag<M, GM>() | xasm_flag<M, GM, P>();  // M with the table placement and exp form (f64)
   (void)kk;  // read through kargs()
@@ -2520,7 +2569,16 @@ tube_fast_kernel(FK kk) {
       }
     } else {
     FCost ca;  // ancillary weights theta (shared by the batch), terminal weight Qa (:885, :891)
-    {
+    if constexpr (Obs<ML>::own) {  // the trajectory's own column of theta [6][B] (every lane of it the same values)
+      const real* th = ((const FKOwn*)kargs())->o.th + i;
+      ca.Q0 = ca.Qf0 = th[0];
+      ca.Q1 = ca.Qf1 = th[nb];
+      ca.Q2 = ca.Qf2 = th[2 * nb];
+      ca.R0 = th[3 * nb];
+      ca.R1 = th[4 * nb];
+      ca.qb = th[5 * nb];
+      ca.tg = f4{0.f, 0.f, 0.f, 0.f};
+    } else {
       const real* th = kargs()->a.theta;
       ca.Q0 = ca.Qf0 = th[0];
       ca.Q1 = ca.Qf1 = th[1];
@@ -2622,6 +2680,10 @@ tube_fast_kernel(FK kk) {
       if (st || h != 0 || !(gm <= a.gbound)) {
 #pragma unroll
         for (int j = 0; j < DTMPC_TUBE_SUMS; ++j) acc[j] = 0.f;
+      }
+      if constexpr (Obs<ML>::own) {  // the trajectory's own update, from its own (masked) gradient row
+        const OwnArgs& o = ((const FKOwn*)K)->o;
+        if (h == 0 && o.upd) own_update(o, nb, i, acc + 1);
       }
       if (h == 0) {
         a.status[i] |= st;
@@ -3179,6 +3241,9 @@ int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, 
 // gamma = 0 record form): the tube step with kk.a.scenes set, the standalone iLQR with kk.a.scenes set
 int launch_tube_fast_scenes(int M, int lanes, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FK& kk);
 int launch_ilqr_fast_scenes(int M, int lanes, bool track, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::IK& kk);
+// the own-theta launches (csrc/dtmpc_fast_own.hip: the kOwn instantiations of the tube step, M obstacles at the
+// gamma = 0 record form, with kScene as well when `scene`): kk.k the step's arguments, kk.o the own-theta block
+int launch_tube_fast_own(int M, int lanes, bool scene, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FKOwn& kk);
 #endif
 
 #ifndef DTMPC_FAST_AUX_TU  // the tube step (this file's own translation unit)
@@ -3266,7 +3331,7 @@ static bool tube_fast_scc(int N, int64_t B, int64_t Bc, int lanes, int g0) {
 #endif
 
 int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_t B, int64_t goff, int64_t step,
-                     const dtmpc_tube_state* S, const void* w, hipStream_t st) {
+                     const dtmpc_tube_state* S, const void* w, hipStream_t st, const dtmpc_own_theta* own) {
   FK_NS::FK kk;
   std::memset(&kk, 0, sizeof(kk));
   fast_p(sp, kk.p);
@@ -3299,6 +3364,22 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
   a.scenes = (const real*)S->scenes;
   if (a.scenes && (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0))  // dtmpc_tube_step has refused these (scenes_unsupported)
     return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes need f32 and dbas_gamma == 0");
+  FK_NS::OwnArgs oa;
+  std::memset(&oa, 0, sizeof(oa));
+  if (own) {  // dtmpc_tube_step_own has refused what the kOwn kernels do not cover; state->theta is not read
+    if (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0 || S->phase != 0 || !own->theta || !own->vel)
+      return set_err(DTMPC_ERR_BAD_ARG, "own theta needs f32, dbas_gamma == 0, the whole step (phase 0), theta and vel");
+    a.theta = nullptr;
+    oa.th = (real*)own->theta;
+    oa.vel = (real*)own->vel;
+    oa.mom = real(own->adapt.momentum);
+    oa.eta = real(own->adapt.lr_eta);
+    oa.qmin = real(own->adapt.q_min);
+    oa.rmin = real(own->adapt.r_min);
+    oa.qbmin = real(own->adapt.qb_min);
+    oa.qbmax = real(own->adapt.qb_max);
+    oa.upd = own->update ? 1 : 0;
+  }
   a.gbound = cf->grad_bound > 0 ? real(cf->grad_bound) : real(__builtin_inf());
   a.disturbance = cf->disturbance;
   a.write_log = (cf->write_log && S->log) ? 1 : 0;
@@ -3353,6 +3434,14 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
 #endif
     (void)gk;
 #if !DTMPC_FAST_F64
+    if (own) {  // own theta (with or without scenes): the kOwn kernels' unit, the same record form
+      FK_NS::FKOwn ko;  // this chunk's arguments, then the own-theta block
+      std::memset(&ko, 0, sizeof(ko));
+      ko.k = kk;
+      ko.o = oa;
+      if (int r = launch_tube_fast_own(sp->n_obstacles, lanes, a.scenes != nullptr, grid, (unsigned)bs, st, ko)) return r;
+      continue;
+    }
     if (a.scenes) {  // per-trajectory scenes: the kScene kernels' unit (the gamma = 0 record form, no sin / cos cache)
       if (int r = launch_tube_fast_scenes(sp->n_obstacles, lanes, grid, (unsigned)bs, st, kk)) return r;
       continue;
@@ -3703,6 +3792,30 @@ int launch_ilqr_fast_scenes(int M, int lanes, bool track, dim3 grid, unsigned bs
 #undef SC_LAUNCH
 }
 #undef SC_M
+
+#elif defined(DTMPC_FAST_OWN_TU)  // the own-theta tube kernels (csrc/dtmpc_fast_own.hip), f32 only
+
+int launch_tube_fast_own(int M, int lanes, bool scene, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FKOwn& kk) {
+#define OWN_LAUNCH(m, l) hipLaunchKernelGGL((FK_NS::tube_fast_kernel<(m), l, 2>), grid, dim3(bs), 0, st, kk)
+#define OWN_LANES(m) \
+  if (lanes == 4) OWN_LAUNCH(m, 4); else if (lanes == 2) OWN_LAUNCH(m, 2); else OWN_LAUNCH(m, 1);
+#define OWN_CASE(m) \
+  case m:           \
+    if (scene) { OWN_LANES(m | FK_NS::kOwn | FK_NS::kScene) } else { OWN_LANES(m | FK_NS::kOwn) } \
+    return 0;
+  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "own-theta tube unit: lanes");
+  switch (M) {
+#ifdef DTMPC_FAST_M_ONLY
+    OWN_CASE(DTMPC_FAST_M_ONLY)
+#else
+    OWN_CASE(1) OWN_CASE(2) OWN_CASE(3) OWN_CASE(4) OWN_CASE(5) OWN_CASE(6) OWN_CASE(7) OWN_CASE(8)
+#endif
+    default: return set_err(DTMPC_ERR_BAD_ARG, "fast tube step with own theta: obstacle count not instantiated");
+  }
+#undef OWN_CASE
+#undef OWN_LANES
+#undef OWN_LAUNCH
+}
 
 #else  // the general path's solves (csrc/dtmpc_fast_general.hip)
 

@@ -853,9 +853,23 @@ int64_t dtmpc_tube_partials_count(int64_t B, int32_t lanes) {
   return (B * lanes + bs - 1) / bs;
 }
 
-int dtmpc_tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg, int64_t B,
-                    int64_t global_offset, int64_t step, const dtmpc_tube_state* state,
-                    const void* w, void* stream) {
+}  // extern "C"
+
+// Why own theta cannot run for this precision / problem / configuration, or NULL when it can
+// (dtmpc_own_theta_supported): the kOwn kernels are the fused f32 tube step at dbas_gamma == 0.
+static const char* own_theta_unsupported(int dtype, const dtmpc_spec* sp, const dtmpc_tube_cfg* cf) {
+  if (dtype != DTMPC_F32) return "own theta: f32 only";
+  if (sp->dbas_gamma != 0.0) return "own theta: dbas_gamma must be 0";
+  if (!tube_fast_eligible(dtype, sp, cf))
+    return "own theta: needs the fused f32 tube kernel (smooth-min over 1 to 8 obstacles, relaxed inverse barrier, "
+           "h_offset 0, unwrapped target cost, six non-zero line-search alphas, DTMPC_FAST not 0)";
+  return nullptr;
+}
+
+// dtmpc_tube_step (own == NULL) and dtmpc_tube_step_own
+static int tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg, int64_t B, int64_t global_offset,
+                     int64_t step, const dtmpc_tube_state* state, const void* w, void* stream,
+                     const dtmpc_own_theta* own) {
   int e = check_spec(spec, B);
   if (e) return e;
   if (!cfg || !state) return set_err(DTMPC_ERR_BAD_ARG, "NULL cfg/state");
@@ -868,7 +882,7 @@ int dtmpc_tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg
   if (cfg->nominal.kind != DTMPC_COST_TARGET) return set_err(DTMPC_ERR_BAD_ARG, "nominal cost must be DTMPC_COST_TARGET");
   const dtmpc_tube_state* S = state;
   if (!S->x || !S->b || !S->xbar || !S->bbar || !S->Xnom || !S->Unom || !S->Xaux || !S->Uaux ||
-      !S->work || !S->theta || !S->partials || !S->status)
+      !S->work || (!own && !S->theta) || !S->partials || !S->status)
     return set_err(DTMPC_ERR_BAD_ARG, "NULL state array");
   if (S->lanes != 1 && S->lanes != 2 && S->lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "state->lanes must be 1, 2 or 4");
   if (S->n_partials < dtmpc_tube_partials_count(B, S->lanes))
@@ -888,6 +902,11 @@ int dtmpc_tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg
     return set_err(DTMPC_ERR_BAD_ARG, "a split step (state->phase 1 / 2) needs the fused kernel and B within one launch "
                                       "chunk of the precision (dtmpc_tube_split_ok)");
   hipStream_t st = (hipStream_t)stream;
+  if (own) {  // never the shared theta in place of the trajectories' own: an unsupported configuration is an error
+    if (const char* why = own_theta_unsupported(dtype, spec, cfg)) return set_err(DTMPC_ERR_BAD_ARG, why);
+    if (!own->theta || !own->vel) return set_err(DTMPC_ERR_BAD_ARG, "own theta: NULL theta or vel");
+    if (S->phase != 0) return set_err(DTMPC_ERR_BAD_ARG, "own theta: no split step (state->phase must be 0)");
+  }
   if (S->scenes) {  // never the shared table in place of the scenes: an unsupported configuration is an error
     const char* why = scenes_unsupported(dtype, spec, &cfg->nom_ilqr);
     if (!why) why = scenes_unsupported(dtype, spec, &cfg->aux_ilqr);
@@ -895,12 +914,33 @@ int dtmpc_tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg
     if (!tube_fast_eligible(dtype, spec, cfg))
       return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes: the nominal cost must not wrap the heading error");
   }
-  if (tube_fast_eligible(dtype, spec, cfg)) return launch_tube_fast(spec, cfg, B, global_offset, step, S, w, st);
+  if (tube_fast_eligible(dtype, spec, cfg)) return launch_tube_fast(spec, cfg, B, global_offset, step, S, w, st, own);
+  if (own) return set_err(DTMPC_ERR_BAD_ARG, "own theta: needs the fused f32 tube kernel");
   if (tube_fast_eligible64(dtype, spec, cfg))
     return launch_tube_fast64(spec, cfg, B, global_offset, step, S, w, st);
   if (dtype == DTMPC_F32) return launch_tube<float>(spec, cfg, B, global_offset, step, S, w, st);
   if (dtype == DTMPC_F64) return launch_tube<double>(spec, cfg, B, global_offset, step, S, w, st);
   return set_err(DTMPC_ERR_BAD_ARG, "bad dtype");
+}
+
+extern "C" {
+
+int dtmpc_tube_step(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg, int64_t B,
+                    int64_t global_offset, int64_t step, const dtmpc_tube_state* state,
+                    const void* w, void* stream) {
+  return tube_step(dtype, spec, cfg, B, global_offset, step, state, w, stream, nullptr);
+}
+
+int dtmpc_tube_step_own(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg, int64_t B,
+                        int64_t global_offset, int64_t step, const dtmpc_tube_state* state,
+                        const void* w, void* stream, const dtmpc_own_theta* own) {
+  if (!own) return set_err(DTMPC_ERR_BAD_ARG, "own theta: NULL dtmpc_own_theta");
+  return tube_step(dtype, spec, cfg, B, global_offset, step, state, w, stream, own);
+}
+
+int32_t dtmpc_own_theta_supported(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg) {
+  if (!spec || !cfg) return 0;
+  return own_theta_unsupported(dtype, spec, cfg) ? 0 : 1;
 }
 
 int32_t dtmpc_tube_split_supported(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg, int32_t lanes) {

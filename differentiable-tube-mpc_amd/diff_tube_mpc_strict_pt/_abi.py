@@ -125,6 +125,17 @@ class DtmpcTubeState(C.Structure):
     ]
 
 
+class DtmpcOwnTheta(C.Structure):
+    """dtmpc_own_theta: per-trajectory ancillary weights of dtmpc_tube_step_own (theta, vel [6][B])."""
+    _fields_ = [
+        ("theta", C.c_void_p),
+        ("vel", C.c_void_p),
+        ("adapt", DtmpcAdaptCfg),
+        ("update", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
 class DtmpcGeneralCfg(C.Structure):
     _fields_ = [
         ("target", C.c_double * 3),
@@ -225,6 +236,12 @@ PROTOTYPES = {
     "dtmpc_tube_reset": (C.c_int, [C.c_int, C.POINTER(DtmpcSpec), I64, P, C.POINTER(DtmpcTubeState), P, P, P, P]),
     "dtmpc_partials_reduce": (C.c_int, [C.c_int, I64, P, P, P]),
     "dtmpc_theta_update": (C.c_int, [C.c_int, C.POINTER(DtmpcAdaptCfg), C.c_double, P, P, P, P]),
+    "dtmpc_own_theta_supported": (I32, [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcTubeCfg)]),
+    "dtmpc_tube_step_own": (
+        C.c_int,
+        [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcTubeCfg), I64, I64, I64, C.POINTER(DtmpcTubeState), P, P,
+         C.POINTER(DtmpcOwnTheta)],
+    ),
     "dtmpc_sensitivity_upper_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64]),
     "dtmpc_ddp_sensitivity_upper": (
         C.c_int,

@@ -105,15 +105,30 @@ class TubeMPC:
       scenes: per-trajectory obstacles and nominal target ([3M + 3, batch], problem.pack_scenes; a shard passes
         its own columns of the global array) or None: every trajectory runs the setup's problem.  Fused f32
         kernels only (dtmpc_scenes_supported); see :meth:`set_scenes`.
+      own_theta: False (default): one theta for the batch, adapted by the batch-mean gradient.  True: trajectory i
+        has its own weights ``theta[:, i]`` and momentum ``vel[:, i]`` (both [6, batch]) and updates them from its
+        own gradient row inside the fused kernel, so the batch is ``batch`` independent closed loops -- each one
+        bitwise the shared mode at batch = 1 on that trajectory.  A step is one fused launch and the partial-sum
+        reduction (``sums`` / ``loss_mean`` report this process's batch); no all-reduce, no update launch.  A process
+        group is accepted and unused by the update; a shard is its rows of the global batch (``global_offset``).
+        Fused f32 kernels at gamma = 0 only (dtmpc_own_theta_supported), no ``overlap``; composes with ``scenes``.
+      theta0: own-theta mode's initial weights, [batch, 6] (this process's rows) or [6]; default: the setup's theta0
+        for every trajectory.  :meth:`reset` restores them and zeroes the momentum.
     """
 
     def __init__(self, setup, *, batch: int, device="cuda", dtype=torch.float32, disturbance: str = "philox",
                  seed: int = 0, global_offset: int = 0, global_batch: Optional[int] = None, process_group=None,
                  write_log: bool = False, record_choices: bool = False, grad_bound: Optional[float] = None,
-                 record_costs: bool = False, overlap: Optional[bool] = None, scenes: Optional[Tensor] = None):
+                 record_costs: bool = False, overlap: Optional[bool] = None, scenes: Optional[Tensor] = None,
+                 own_theta: bool = False, theta0: Optional[Tensor] = None):
         if isinstance(setup, dict):
             setup = paper_setup_from_config(setup)
         self.setup: PaperSetup = setup
+        self.own_theta = bool(own_theta)
+        if theta0 is not None and not self.own_theta:
+            raise ValueError("theta0 goes with own_theta=True (the shared mode starts from the setup's theta0)")
+        if self.own_theta and overlap:
+            raise ValueError("own_theta has no overlap mode: there is no collective to overlap")
         self.B = int(batch)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -172,6 +187,31 @@ class TubeMPC:
         self._theta0 = torch.tensor(setup.theta0, **kw)
         self._theta = self._theta0.clone()
         self._vel = torch.zeros(6, **kw)
+        if self.own_theta:
+            if not self.lib.dtmpc_own_theta_supported(self._dt, C.byref(self.spec), C.byref(self.cfg)):
+                raise ValueError("own_theta is not supported for this dtype / problem / configuration "
+                                 "(dtmpc_own_theta_supported: f32, the fused tube kernel's configuration, gamma = 0, "
+                                 "DTMPC_FAST not 0)")
+            # dtmpc_tube_reset still restores a shared [6] pair: these two, which no own-theta launch reads
+            self._theta_sh, self._vel_sh = self._theta, self._vel
+            if theta0 is None:
+                t0 = self._theta0[:, None].expand(6, B)
+            else:
+                t0 = torch.as_tensor(theta0).to(**kw)
+                if tuple(t0.shape) == (6,):
+                    t0 = t0[:, None].expand(6, B)
+                elif tuple(t0.shape) == (B, 6):
+                    t0 = t0.t()
+                else:
+                    raise ValueError(f"theta0 must be [{B}, 6] or [6], got {tuple(t0.shape)}")
+            self._theta0_own = t0.contiguous()  # [6, B]
+            self._theta = self._theta0_own.clone()
+            self._vel = torch.zeros(6, B, **kw)
+            own = _abi.DtmpcOwnTheta()
+            own.theta, own.vel = self._theta.data_ptr(), self._vel.data_ptr()
+            own.adapt = self.adapt
+            own.update = 1
+            self._own = own
         self._theta_ready = None  # event on the side stream: the last step's theta update is done
         self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.iters = torch.zeros(2, B, dtype=torch.int32, device=self.device)
@@ -188,7 +228,7 @@ class TubeMPC:
         st.x, st.b, st.xbar, st.bbar = (t.data_ptr() for t in (self.x, self.b, self.xbar, self.bbar))
         st.Xnom, st.Unom, st.Xaux, st.Uaux = (t.data_ptr() for t in (self.Xnom, self.Unom, self.Xaux, self.Uaux))
         st.work = self.work.data_ptr()
-        st.theta = self._theta.data_ptr()
+        st.theta = (self._theta_sh if self.own_theta else self._theta).data_ptr()
         st.partials = self.partials.data_ptr()
         st.log = self.log.data_ptr() if self.log is not None else None
         st.status = self.status.data_ptr()
@@ -216,7 +256,7 @@ class TubeMPC:
                                                 self.chunk))
         if overlap and not can:
             raise ValueError("overlap needs the fused tube kernel and B within one launch chunk (dtmpc_tube_split_ok)")
-        self.overlap = bool(can and (multi if overlap is None else overlap))
+        self.overlap = bool(can and (multi if overlap is None else overlap)) and not self.own_theta
         self._side = torch.cuda.Stream(device=self.device) if self.overlap else None
         if scenes is not None:
             self.set_scenes(scenes)
@@ -251,13 +291,14 @@ class TubeMPC:
     # step's theta update, wherever overlap mode put it
     @property
     def theta(self) -> Tensor:
-        """[6] shared ancillary weights Qa(3), Ra(2), qba after the last step's update."""
+        """[6] shared ancillary weights Qa(3), Ra(2), qba after the last step's update; own-theta mode: [6, batch],
+        column i trajectory i's."""
         self.join()
         return self._theta
 
     @property
     def vel(self) -> Tensor:
-        """[6] momentum of the theta update."""
+        """[6] momentum of the theta update; own-theta mode: [6, batch]."""
         self.join()
         return self._vel
 
@@ -269,7 +310,7 @@ class TubeMPC:
 
     def reset(self, x0: Tensor, U_nom0: Optional[Tensor] = None, U_aux0: Optional[Tensor] = None) -> None:
         """x0 [B, 3]: plant and nominal start at x0, b0 = B(h(x0)) (core/tube_mpc.py:770-779);
-        warm starts default to zero; theta and momentum restart from the setup."""
+        warm starts default to zero; theta and momentum restart from the setup (own-theta mode: from ``theta0``)."""
         if x0.shape != (self.B, 3):
             raise ValueError(f"x0 must be [{self.B}, 3]")
         self.join()
@@ -278,8 +319,13 @@ class TubeMPC:
             x0c = x0.to(device=self.device, dtype=self.dtype).contiguous()
             _lib.check(self.lib.dtmpc_tube_reset(self._dt, C.byref(self.spec), self.B, x0c.data_ptr(),
                                                  C.byref(self.state), self._theta0.data_ptr(),
-                                                 self._theta.data_ptr(), self._vel.data_ptr(), self._stream()),
+                                                 (self._theta_sh if self.own_theta else self._theta).data_ptr(),
+                                                 (self._vel_sh if self.own_theta else self._vel).data_ptr(),
+                                                 self._stream()),
                        "dtmpc_tube_reset")
+            if self.own_theta:
+                self._theta.copy_(self._theta0_own)
+                self._vel.zero_()
             self.t = 0
             return
         xs = x0.to(device=self.device, dtype=self.dtype).t().contiguous()
@@ -299,7 +345,7 @@ class TubeMPC:
             self.Unom.copy_(U_nom0.to(self.Unom).permute(1, 2, 0))
         if U_aux0 is not None:
             self.Uaux.copy_(U_aux0.to(self.Uaux).permute(1, 2, 0))
-        self._theta.copy_(self._theta0)
+        self._theta.copy_(self._theta0_own if self.own_theta else self._theta0)
         self._vel.zero_()
         self.status.zero_()
         self.t = 0
@@ -315,7 +361,9 @@ class TubeMPC:
         (ADVICE r05); a pair is accepted there too and then spans both launches and the wait.
         adapt=False: theta is held (no partial-sum reduction, all-reduce or update) -- the tube MPC of
         BASELINE config 3 without the adaptation step of config 4; the IFT pass still runs in the fused
-        kernel (its per-trajectory rows land in the log)."""
+        kernel (its per-trajectory rows land in the log).
+        Own-theta mode: one fused launch, in which every trajectory also updates its own column of theta and vel
+        (adapt=False: holds them), then the partial-sum reduction for ``sums``; no all-reduce, no update launch."""
         wp = None
         if self.cfg.disturbance == 0:
             if w is None or w.shape != (self.B, 3):
@@ -338,11 +386,23 @@ class TubeMPC:
             if len(ev) == 4:
                 ev[2].record()
             self._launch(2, wp, s)
+        elif self.own_theta:
+            self.state.phase = 0
+            self._own.adapt = self.adapt
+            self._own.update = 1 if adapt else 0
+            _lib.check(self.lib.dtmpc_tube_step_own(self._dt, C.byref(self.spec), C.byref(self.cfg), self.B,
+                                                    self.global_offset, self.t, C.byref(self.state), wp, s,
+                                                    C.byref(self._own)), "dtmpc_tube_step_own")
         else:
             self._launch(0, wp, s)
         if ev:
             ev[-1].record()
         if not adapt:
+            self.t += 1
+            return
+        if self.own_theta:  # theta and vel were updated per trajectory inside the launch
+            _lib.check(self.lib.dtmpc_partials_reduce(self._dt, self.n_partials, self.partials.data_ptr(),
+                                                      self._sums.data_ptr(), s), "dtmpc_partials_reduce")
             self.t += 1
             return
         if self.overlap:

@@ -399,6 +399,44 @@ int dtmpc_partials_reduce(int dtype, int64_t n_partials, const void* partials, v
 int dtmpc_theta_update(int dtype, const dtmpc_adapt_cfg* cfg, double inv_batch, const void* sums,
                        void* theta, void* velocity, void* stream);
 
+/* ---- own theta: per-trajectory ancillary weights ----------------------------------------- */
+/*
+ * The shared mode above adapts ONE theta for the batch from the batch-mean gradient.  In own-theta mode trajectory i
+ * has its own weights theta[:, i] and momentum vel[:, i] (SoA [6][B] in the batch dtype, element (j, i) at
+ * j * B + i; rows Qa(3), Ra(2), qba): its ancillary solve and sensitivity pass use them, and at the end of the
+ * step it updates them from its OWN gradient row -- inside the fused kernel, with dtmpc_theta_update's arithmetic
+ * and roundings (vel = momentum vel + g; theta = project(theta - lr_eta vel)).  Trajectory i is then exactly the
+ * shared mode run at B = 1 on trajectory i alone: a batch is B independent closed loops, with no reduction, no
+ * collective and no update launch between its steps.  A trajectory the health policy leaves out of a step (status
+ * set, or a gradient component above cfg->grad_bound or non-finite) updates with g = 0: its momentum still decays
+ * and moves theta, as the shared update does at B = 1 with no healthy trajectory.
+ * f32 fused kernels at dbas_gamma == 0 only (csrc/dtmpc_fast_own.hip); there is no generic-kernel, f64 or
+ * split-step form: those return DTMPC_ERR_BAD_ARG, never the shared theta.  Added beside ABI 8: its structs
+ * and entry points are unchanged, the mode is discovered through dtmpc_own_theta_supported. */
+typedef struct dtmpc_own_theta {
+  void* theta;            /* [6][B] in/out */
+  void* vel;              /* [6][B] in/out */
+  dtmpc_adapt_cfg adapt;
+  int32_t update;         /* 0: hold theta (still read per trajectory) */
+  int32_t pad;
+} dtmpc_own_theta;
+
+/* 1 when dtmpc_tube_step_own runs this precision / problem / configuration: DTMPC_F32, the fused tube kernel's
+ * configuration (smooth-min over 1..8 obstacles, relaxed inverse barrier, h_offset == 0, unwrapped target cost, six
+ * non-zero line-search alphas in both solves, DTMPC_FAST not 0 in the environment) and dbas_gamma == 0; else 0.
+ * Host-only. */
+int32_t dtmpc_own_theta_supported(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg);
+
+/* dtmpc_tube_step in own-theta mode: state->theta is ignored (own->theta column i is trajectory i's), state->scenes
+ * is honoured, state->phase must be 0; the log rows, status, iters, choices, costs and state->partials are written
+ * as by dtmpc_tube_step (so dtmpc_partials_reduce still gives the batch's sums).  own->update != 0: every
+ * trajectory then updates its column of theta and vel.  Chunked launches (state->chunk) index the columns within
+ * the whole batch.  DTMPC_ERR_BAD_ARG, before any device call, where dtmpc_own_theta_supported is 0, own or
+ * one of its arrays is NULL, or state->phase != 0. */
+int dtmpc_tube_step_own(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg* cfg, int64_t B,
+                        int64_t global_offset, int64_t step, const dtmpc_tube_state* state,
+                        const void* w, void* stream, const dtmpc_own_theta* own);
+
 
 /* ---- general (softplus / tanh parameterised) IFT path ------------------------------------ */
 /*
