@@ -897,13 +897,34 @@ struct Scc {
 };
 template <>
 struct Scc<false> {};
+// Sparse state rows (XS > 0; the sin / cos cache form only): between the passes of one solve the workspace holds the X
+// rows whose index is a multiple of XS, and row N; the backward pass re-rolls x, y, theta of the rows between from the
+// stored row below them, the U rows and sc[k] (dubins_sc -- the re-roll the line search and the commit already take
+// their old-tape states from, bit for bit), and the one value of a row that no re-roll gives cheaply, the barrier state
+// b_k, sits in a second table behind the sin / cos pairs: bt[k][threadIdx.x], k = 0..N, written by init_tape and the
+// commit with the b they compute anyway (own column only: no barrier).  The other X rows are neither written nor read
+// until the solve's end, where copy_out_sparse makes the rows dense again for every reader outside the solve.
+// Dynamic LDS: N * 8 * blockDim (sc) + (N + 1) * 4 * blockDim (bt) bytes.
+constexpr int kXStride = 5;  // the shipped stride (2 and 10 measured: DESIGN.md section 3)
+template <bool ON>
+struct Bt {
+  unsigned lo, rs;  // this lane's byte offset in row 0 (behind the sin / cos table), the row stride (blockDim.x * 4)
+  __device__ __forceinline__ real* at(int k) const { return (real*)((char*)scc_tab + ((unsigned)k * rs + lo)); }
+  __device__ __forceinline__ real ld(int k) const { return *at(k); }
+  __device__ __forceinline__ void st(int k, real b) const { *at(k) = b; }
+};
+template <>
+struct Bt<false> {};
 
-template <bool TRACK, bool G0, bool RG0, int P, int NCV = NC, bool RROLL = true, bool SCC = false>
+template <bool TRACK, bool G0, bool RG0, int P, int NCV = NC, bool RROLL = true, bool SCC = false, int XS = 0>
 struct Solve {
   static_assert(NCV == NC || (NCV == 4 && P != 4), "four lanes split six candidates");
   static_assert(!SCC || (P == 1 && G0 && !DTMPC_FAST_F64), "the sin / cos cache: f32, one lane, gamma = 0 records");
   static constexpr bool scc = SCC;  // the heading's sin / cos of the current tape in LDS (Scc)
   Scc<SCC> sc;
+  static_assert(XS == 0 || (SCC && XS > 1), "sparse state rows go with the sin / cos cache");
+  static constexpr int xs = XS;  // > 0: the X rows of the workspace are sparse between the passes (Bt)
+  Bt<(XS > 0)> bt;
   static constexpr bool rroll = RROLL;
   static constexpr bool g0 = G0;    // gamma = 0: the compact gain records (Gains)
   static constexpr bool ric0 = RG0; // gamma = 0: the Riccati step without the barrier state's zero column
@@ -1011,6 +1032,54 @@ __device__ __forceinline__ void copy_out(int N, const Rsrc& r, const RA& XA, con
   }
 }
 
+// ... of a solve with sparse state rows (Solve::xs): x, y, theta rolled forward from x0 over the U rows with the table's
+// sin / cos (dubins_sc, the step that wrote the tape), b from its table; out to the ABI arrays as above, and the rows
+// the passes left out into the workspace, so that every reader after the solve (the ancillary's references, the
+// sensitivity pass, the split step's second launch, the plant) finds dense rows
+template <bool SHIFT = true, class SV>
+__device__ __forceinline__ void copy_out_sparse(const FP& p, const real* x0, const SV& S) {
+  DTMPC_NOCONTRACT
+  constexpr int XS = SV::xs;
+  const int N = p.N, N1 = N - 1;
+  auto iu = [&](int j) { return uidx(j < N1 ? j : N1); };
+  real a0 = x0[0], a1 = x0[1], a2 = x0[2];
+  f2 uq[3];
+  uq[0] = S.u(0);
+  uq[1] = S.u(iu(1));
+  for (int k = 0; k <= N; k += 3) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int kk = k + j;
+      uq[(j + 2) % 3] = S.u(iu(kk + 2));
+      if (kk > N) break;
+      const real b = S.bt.ld(kk);
+      S.X.st(kk, 0, a0);
+      S.X.st(kk, 1, a1);
+      S.X.st(kk, 2, a2);
+      S.X.st(kk, 3, b);
+      if (kk % XS != 0 && kk != N) S.stx(kk, f4{a0, a1, a2, b});
+      if (kk < N) {
+        const f2 u = uq[j];
+        if (!SHIFT) {
+          S.U.st(kk, 0, u.x);
+          S.U.st(kk, 1, u.y);
+        } else {
+          if (kk > 0) {
+            S.U.st(kk - 1, 0, u.x);
+            S.U.st(kk - 1, 1, u.y);
+          }
+          if (kk == N1) {
+            S.U.st(kk, 0, u.x);
+            S.U.st(kk, 1, u.y);
+          }
+        }
+        const f2 t = S.sc.ld(kk);
+        dubins_sc(p, a0, a1, a2, u.x, u.y, t.x, t.y);
+      }
+    }
+  }
+}
+
 // iLQR start (init_tape): V = clamp(V_init) (the warm start, ABI SoA), X = rollout(x0, V) into this
 // solve's records, and the alpha = 0 candidate's cost
 template <bool TRACK, int M, class SV>
@@ -1021,6 +1090,7 @@ __device__ __forceinline__ real init_tape(const FP& p, const FCost& c, const rea
   real s0 = x0[0], s1 = x0[1], s2 = x0[2], sb = x0[3];
   real Bc = barrier_at<M>(p, x0[0], x0[1]);
   S.stx(0, f4{s0, s1, s2, sb});
+  if constexpr (SV::xs > 0) S.bt.st(0, sb);
   real J = 0.f;
   real n0 = S.U.ld(0, 0), n1 = S.U.ld(0, 1);
   f4 nR = f4{0.f, 0.f, 0.f, 0.f};
@@ -1051,7 +1121,12 @@ __device__ __forceinline__ real init_tape(const FP& p, const FCost& c, const rea
     } else {
       fhat<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc);
     }
-    S.stx(k + 1, f4{s0, s1, s2, sb});
+    if constexpr (SV::xs > 0) {  // the stored rows only (a uniform test), b of every row into the table
+      S.bt.st(k + 1, sb);
+      if ((k + 1) % SV::xs == 0 || k + 1 == N) S.stx(k + 1, f4{s0, s1, s2, sb});
+    } else {
+      S.stx(k + 1, f4{s0, s1, s2, sb});
+    }
   }
   if (!want_cost) return 0.f;
   f4 R = f4{0.f, 0.f, 0.f, 0.f};
@@ -1325,6 +1400,23 @@ __device__ __forceinline__ Lin lin_point_sc(const FP& p, const f4& X, f2 sc) {
   return L;
 }
 
+// sparse state rows (Solve::xs): x, y, theta of rows g .. g + XS - 1 from the stored row X0 = X[g], the controls V[j] = U[g + j]
+// and sc[j] = the table's (sin, cos) of theta_{g + j} -- the Dubins part of the step that wrote the tape, operation for
+// operation (dubins_sc), so the rows are bit for bit those the dense form stores
+template <int XS>
+__device__ __forceinline__ void reroll_group(const FP& p, const f4& X0, const f2* V, const f2* sc, real* r0, real* r1,
+                                             real* r2) {
+  DTMPC_NOCONTRACT
+  real a0 = X0.x, a1 = X0.y, a2 = X0.z;
+#pragma unroll
+  for (int j = 0; j < XS; ++j) {
+    r0[j] = a0;
+    r1[j] = a1;
+    r2[j] = a2;
+    if (j + 1 < XS) dubins_sc(p, a0, a1, a2, V[j].x, V[j].y, sc[j].x, sc[j].y);
+  }
+}
+
 // backward pass (ilqr_backward, core/ddp.py:172-254).  P > 1: the per-point linearisation (sin / cos,
 // grad h, B' -- about a third of a step) is computed for P steps at once, one step per lane of the
 // trajectory, and handed to every lane by DPP broadcasts; the Riccati recursion itself is sequential
@@ -1372,8 +1464,9 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
   bool ok = finite(R.vx(0)) && finite(R.vx(1)) && finite(R.vx(2)) && finite(R.vx(3));
   // step inputs one step ahead (P > 1: none, every step takes its inputs from the group's rows by broadcast)
   constexpr bool BCI = P > 1;
-  f4 nX = BCI ? f4{0.f, 0.f, 0.f, 0.f} : S.x(N - 1), nR = f4{0.f, 0.f, 0.f, 0.f};
-  f2 nV = BCI ? f2{0.f, 0.f} : S.u(N - 1), nQ = f2{0.f, 0.f};
+  constexpr bool GRP = P == 1 && SV::xs > 0;  // sparse state rows: the tape's rows by groups (below), row N - 1 may not exist
+  f4 nX = BCI || GRP ? f4{0.f, 0.f, 0.f, 0.f} : S.x(N - 1), nR = f4{0.f, 0.f, 0.f, 0.f};
+  f2 nV = BCI || GRP ? f2{0.f, 0.f} : S.u(N - 1), nQ = f2{0.f, 0.f};
   if (TRACK && !BCI) {
     nR = S.xr(N - 1);
     nQ = S.ur(N - 1);
@@ -1416,7 +1509,48 @@ __device__ __forceinline__ bool backward(const FP& p, const FCost& c, real reg, 
       }
     }
   };
-  if (P == 1) {
+  if constexpr (P == 1 && SV::xs > 0) {
+    // sparse state rows: the horizon in groups of XS steps, the top (possibly ragged) group first.  Group g (a stored
+    // row) holds steps g .. g + XS - 1: its stored row and its U rows are read one group ahead, x, y, theta of its
+    // other rows re-rolled (reroll_group), b of every row taken from the table; the inner loop is unrolled, so the
+    // group's states are registers under static indices.  The steps themselves are the dense form's.
+    constexpr int XS = SV::xs;
+    const int N1 = N - 1;
+    f4 gX;
+    f2 gU[XS];
+    auto load_group = [&](int g) {
+      gX = S.x(uidx(g));
+#pragma unroll
+      for (int j = 0; j < XS; ++j) gU[j] = S.u(uidx(g + j < N1 ? g + j : N1));
+    };
+    int g = N1 / XS * XS;
+    load_group(g);
+    for (; g >= 0; g -= XS) {
+      const f4 X0 = gX;
+      f2 V[XS], sc[XS];
+#pragma unroll
+      for (int j = 0; j < XS; ++j) {
+        V[j] = gU[j];
+        sc[j] = S.sc.ld(g + j < N1 ? g + j : N1);
+      }
+      if (g >= XS) load_group(g - XS);
+      real r0[XS], r1[XS], r2[XS];
+      reroll_group<XS>(p, X0, V, sc, r0, r1, r2);
+#pragma unroll
+      for (int j = XS - 1; j >= 0; --j) {
+        const int k = g + j;
+        if (k > N1) continue;  // the ragged top group (uniform)
+        const f4 Rr = nR;
+        const f2 Q = nQ;
+        if (TRACK && k > 0) {
+          nR = S.xr(k - 1);
+          nQ = S.ur(k - 1);
+        }
+        const f4 X = f4{r0[j], r1[j], r2[j], S.bt.ld(k)};
+        step(X, V[j], Rr, Q, k, lin_point_sc<M>(p, X, sc[j]));
+      }
+    }
+  } else if (P == 1) {
     for (int k = N - 1; k >= 0; --k) {
       const f4 X = nX, Rr = nR;
       const f2 V = nV, Q = nQ;
@@ -2008,8 +2142,54 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
     } else {
       fhat<M, SV::g0>(p, s0, s1, s2, sb, u0, u1, Bc);
     }
-    S.stx(k + 1, f4{s0, s1, s2, sb});
+    if constexpr (SV::xs > 0)
+      S.bt.st(k + 1, sb);  // sparse state rows: b of every row into the table, the stored rows by the loop below
+    else
+      S.stx(k + 1, f4{s0, s1, s2, sb});
   };
+  if constexpr (SV::xs > 0) {
+    // Sparse state rows: the loop is unrolled over whole groups of XS steps (RB steps: one group, or as many as hold
+    // LEAD + 1 steps), so the one X store of a group (its top row, after the group's last step) stands at fixed
+    // places of the body and every wait count in it is exact -- a store under a branch in the step would make the
+    // compiler wait for the shorter path's count and cut the prefetch lead on the others.  RB buffers in rotation,
+    // each refilled LEAD steps before use (LEAD + 1 of them live at a time).  Row N, where it is no multiple of XS,
+    // is stored after the loop.  The loop is entered with the outstanding vector-memory operations its back edge
+    // carries -- (refill, U store), (refill, U store, X store) -- by rewriting X row 0 with x0, the value it holds,
+    // between and after the preloads.
+    constexpr int XS = SV::xs, LEAD = kCmLead, RB = (LEAD + XS) / XS * XS;
+    static_assert(LEAD == 2 && RB > LEAD && RB % XS == 0, "the entry sequence below is written for two steps of lead");
+    const int N1 = N - 1;
+    auto ix = [&](int j) { return uidx(j < N1 ? j : N1); };
+    const f4 X0v = f4{x0[0], x0[1], x0[2], x0[3]};
+    StepIn Bf[RB];
+    load_step<false, LX>(Bf[0], T0, ix(0));
+    rst2(S.r, S.XA, 0, 0, f2{X0v.x, X0v.y});
+    load_step<false, LX>(Bf[1], T0, ix(1));
+    rst2(S.r, S.XA, 0, 0, f2{X0v.x, X0v.y});
+    S.stx(0, X0v);
+    // whole groups in the loop, without a way out of its body: an early exit inside it reaches the loop header again
+    // through the latch (the compiler gives a loop one exit), and the header's wait counts are then merged with that
+    // path's shorter queue -- the dense form's loop waits for all but its newest refill in the first step of each trip
+    int k = 0;
+    for (; k + RB <= N; k += RB) {
+#pragma unroll
+      for (int j = 0; j < RB; ++j) {
+        load_step<false, LX>(Bf[(j + LEAD) % RB], T0, ix(k + j + LEAD));
+        step(Bf[j], k + j);
+        if ((j + 1) % XS == 0) S.stx(k + j + 1, f4{s0, s1, s2, sb});
+      }
+    }
+    // the ragged end (N % RB steps, the buffers' rotation goes on) and its row N
+#pragma unroll
+    for (int j = 0; j < RB - 1; ++j) {
+      if (k + j >= N) break;
+      load_step<false, LX>(Bf[(j + LEAD) % RB], T0, ix(k + j + LEAD));
+      step(Bf[j], k + j);
+      if ((j + 1) % XS == 0) S.stx(k + j + 1, f4{s0, s1, s2, sb});
+    }
+    if (N % XS != 0) S.stx(N, f4{s0, s1, s2, sb});
+    return;
+  }
   // R = LEAD + 1 step buffers in rotation: each refilled LEAD steps before it is used (the commit's step
   // is short, ~190 instructions, and a loaded chip stretches an HBM read past one or two of them; one step
   // of lead measured 3 % slower).
@@ -2145,7 +2325,11 @@ __device__ __forceinline__ int ilqr(const FP& p, const FCost& c, const FIlqr& cf
     have_prev = true;
     prev = bestJ;
   }
-  copy_out<SHIFT>(p.N, S.r, S.XA, S.UA, S.X, S.U);  // the tape as it stands (a failed solve's too)
+  // the tape as it stands (a failed solve's too)
+  if constexpr (SV::xs > 0)
+    copy_out_sparse<SHIFT>(p, x0, S);
+  else
+    copy_out<SHIFT>(p.N, S.r, S.XA, S.UA, S.X, S.U);
   return st;
 }
 
@@ -2473,11 +2657,13 @@ constexpr int tab_flag() {
 
 // GM: 0 general, 1 gamma = 0 gain records, 2 gamma = 0 gain records + Riccati step (the default at gamma = 0),
 // 3 (f32, one lane): 2 with the tape's heading sin / cos cached in dynamic LDS (Scc; launch_tube_fast's rule)
+// 4 (f32, one lane): 3 with sparse state rows between the passes of a solve (Bt, kXStride; launch_tube_fast's rule)
 // One wave per SIMD at every lane count (amdgpu_waves_per_eu(1, 1)): the whole 512-register budget.
 template <int M, int P, int GM>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1)))
 tube_fast_kernel(typename FKOf<M>::type kk) {
   constexpr bool G0 = GM > 0, RG0 = GM > 1, SCC = GM > 2;
+  constexpr int XS = GM > 3 ? kXStride : 0;
   constexpr int ML = M | tab_flag<M, GM>() | xasm_flag<M, GM, P>();  // M with the table placement and exp form (f64)
   (void)kk;  // read through kargs()
   __shared__ f4 lds[kBlock / 64 * DTMPC_TUBE_SUMS / 4];  // the workgroup sums at the end
@@ -2527,8 +2713,9 @@ tube_fast_kernel(typename FKOf<M>::type kk) {
     // the split step's hand-over (phase 1 -> 2): the nominal tape's final record offsets (P = 4: its slot) and
     // the nominal solve's status and iterations, [3][Bc] ints after the records
     int* const hand = (int*)((char*)kargs()->a.work + kargs()->a.oPH) + t;
-    Solve<false, G0, RG0, P, NC, true, SCC> Sn;
+    Solve<false, G0, RG0, P, NC, true, SCC, XS> Sn;
     if constexpr (SCC) Sn.sc = Scc<true>{threadIdx.x * 8u, blockDim.x * 8u};
+    if constexpr (XS > 0) Sn.bt = Bt<true>{(unsigned)kargs()->p.N * (blockDim.x * 8u) + threadIdx.x * 4u, blockDim.x * 4u};
     if (phase == 2) {  // the nominal was solved by this step's phase-1 launch
       KArg* K = kargs();
       Sn.r = __builtin_amdgcn_make_buffer_rsrc(K->a.work, 0, (int)K->a.wsz, 0x00020000);
@@ -2588,8 +2775,9 @@ tube_fast_kernel(typename FKOf<M>::type kk) {
       ca.qb = th[5];
       ca.tg = f4{0.f, 0.f, 0.f, 0.f};
     }
-    Solve<true, G0, RG0, P, NC, true, SCC> Sa;
+    Solve<true, G0, RG0, P, NC, true, SCC, XS> Sa;
     if constexpr (SCC) Sa.sc = Sn.sc;  // the ancillary solve's start rollout fills the table again
+    if constexpr (XS > 0) Sa.bt = Sn.bt;
     {  // ancillary MPC tracking the nominal plan (:863-909)
       KArg* K = kargs();
       Sa.r = __builtin_amdgcn_make_buffer_rsrc(K->a.work, 0, (int)K->a.wsz, 0x00020000);
@@ -3231,7 +3419,8 @@ static void fast_p(const dtmpc_spec* sp, FK_NS::FP& p) {
 #if DTMPC_FAST_ILP_SPLIT
 // the tube step's launches of the split units (dtmpc_fast_ilp.hip / dtmpc_fast64_ilp.hip): M obstacles, lanes 1 (or
 // 2 where DTMPC_FAST_ILP_P2), record form g0
-// (g0 = 3: the f32 one-lane form with the sin / cos cache, shm its table's bytes of dynamic LDS; else shm = 0)
+// (g0 = 3: the f32 one-lane form with the sin / cos cache, 4: the same with sparse state rows, shm their tables' bytes of
+// dynamic LDS; else shm = 0)
 int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, unsigned shm, hipStream_t st,
                               const FK_NS::FK& kk);
 #endif
@@ -3328,6 +3517,23 @@ static bool tube_fast_scc(int N, int64_t B, int64_t Bc, int lanes, int g0) {
   const int64_t bs = tube_block(B, lanes);
   return (Bc + bs - 1) / bs * bs <= lane_slots();
 }
+// Sparse state rows (FK_NS::Bt, tube_fast_kernel<M, 1, 4>): the stride a launch runs with, 0 for dense rows.  Taken where
+// the sin / cos cache kernel is taken and both tables fit beside the static sums with 256 lanes on a CU -- one
+// 256-thread workgroup, or four 64-thread ones with their own static sums each: (8 N + 4 (N + 1)) * 256 + 4 * sums
+// <= 160 KiB, i.e. N <= kSparseMaxN = 52.  Longer horizons, up to kSccMaxN, keep the sin / cos cache kernel with dense
+// rows.  DTMPC_FAST_XROWS=dense (environment, read at each call) forces dense rows (A/B, tests); DTMPC_FAST_SCC=0
+// forces the kernel without either table as before.
+constexpr int kSparseMaxN = 52;
+constexpr int64_t kCuLds = 160 * 1024, kTubeSumsLds = kBlock / 64 * DTMPC_TUBE_SUMS * 4;  // tube_fast_kernel's `lds`
+constexpr int64_t sparse_lds(int N) { return ((int64_t)N * 8 + (int64_t)(N + 1) * 4) * 256 + 4 * kTubeSumsLds; }
+static_assert(kSparseMaxN <= kSccMaxN && sparse_lds(kSparseMaxN) <= kCuLds && sparse_lds(kSparseMaxN + 1) > kCuLds,
+              "kSparseMaxN is the longest horizon whose two tables fit a CU's LDS at 256 lanes");
+static int tube_fast_xs(int N, int64_t B, int64_t Bc, int lanes, int g0) {
+  if (const char* e = getenv("DTMPC_FAST_XROWS"))
+    if (!std::strcmp(e, "dense")) return 0;
+  if (!tube_fast_scc(N, B, Bc, lanes, g0) || N > kSparseMaxN) return 0;
+  return FK_NS::kXStride;
+}
 #endif
 
 int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_t B, int64_t goff, int64_t step,
@@ -3423,13 +3629,18 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
     a.wsz = f.wsz;
     const int bs = tube_block(B, lanes);  // 64 while the batch leaves SIMDs idle: one wave per workgroup
     const dim3 grid = dim3((unsigned)((Bc * lanes + bs - 1) / bs));
-    // this launch's kernel form: g0, or 3 -- the sin / cos cache with its [N][bs] table of 8-byte pairs as dynamic LDS
+    // this launch's kernel form: g0, or 3 -- the sin / cos cache with its [N][bs] table of 8-byte pairs as dynamic LDS,
+    // or 4 -- 3 with sparse state rows and the [N + 1][bs] table of b behind the pairs
     int gk = g0;
     unsigned shm = 0;
 #if !DTMPC_FAST_F64
     if (tube_fast_scc(N, B, Bc, lanes, g0)) {
       gk = 3;
       shm = (unsigned)N * 8u * (unsigned)bs;
+      if (tube_fast_xs(N, B, Bc, lanes, g0)) {
+        gk = 4;
+        shm += (unsigned)(N + 1) * 4u * (unsigned)bs;
+      }
     }
 #endif
     (void)gk;
@@ -3448,12 +3659,12 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
     }
 #endif
 #define FAST_LAUNCH(m, l, g) \
-  hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) == 3 ? shm : 0u, st, kk)
+  hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) >= 3 ? shm : 0u, st, kk)
 #define FAST_LANES(m, l) \
   if (g0 == 2) FAST_LAUNCH(m, l, 2); else if (g0) FAST_LAUNCH(m, l, 1); else FAST_LAUNCH(m, l, 0);
 #ifdef DTMPC_FAST_ISA_ONLY  // ISA inspection builds: one instantiation (lanes 1, gamma = 0 records + Riccati)
 #ifndef DTMPC_FAST_ISA_GM
-#define DTMPC_FAST_ISA_GM 2  // 3: the sin / cos cache form (lanes 1)
+#define DTMPC_FAST_ISA_GM 2  // 3: the sin / cos cache form, 4: with sparse state rows (lanes 1)
 #endif
 #define FAST_CASE(m) \
   case m:            \
@@ -3477,7 +3688,7 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
 #define FAST_LANES_P1(m) FAST_LANES(m, 1)
 #else
 #define FAST_LANES_P1(m) \
-  if (gk == 3) FAST_LAUNCH(m, 1, 3); else { FAST_LANES(m, 1) }
+  if (gk == 4) FAST_LAUNCH(m, 1, 4); else if (gk == 3) FAST_LAUNCH(m, 1, 3); else { FAST_LANES(m, 1) }
 #endif
 #if DTMPC_FAST_ILP_P2
 #define FAST_LANES_P2(m) \
@@ -3508,14 +3719,14 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
 int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, unsigned shm, hipStream_t st,
                               const FK_NS::FK& kk) {
 #define ILP_LAUNCH(m, l, g) \
-  hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) == 3 ? shm : 0u, st, kk)
+  hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) >= 3 ? shm : 0u, st, kk)
 #define ILP_LANES(m, l) \
   if (g0 == 2) ILP_LAUNCH(m, l, 2); else if (g0) ILP_LAUNCH(m, l, 1); else ILP_LAUNCH(m, l, 0);
 #if DTMPC_FAST_F64
 #define ILP_LANES1(m) ILP_LANES(m, 1)
-#else  // f32 at one lane: g0 = 3 is the sin / cos cache form
+#else  // f32 at one lane: g0 = 3 is the sin / cos cache form, 4 the same with sparse state rows
 #define ILP_LANES1(m) \
-  if (g0 == 3) ILP_LAUNCH(m, 1, 3); else { ILP_LANES(m, 1) }
+  if (g0 == 4) ILP_LAUNCH(m, 1, 4); else if (g0 == 3) ILP_LAUNCH(m, 1, 3); else { ILP_LANES(m, 1) }
 #endif
 #if DTMPC_FAST_ILP_P2
 #define ILP_CASE(m)         \
@@ -3533,7 +3744,7 @@ int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, 
     return 0;
 #endif
   if (lanes != 1 && !(DTMPC_FAST_ILP_P2 && lanes == 2)) return set_err(DTMPC_ERR_BAD_ARG, "split tube unit: lanes");
-  if (g0 == 3 && (lanes != 1 || DTMPC_FAST_F64)) return set_err(DTMPC_ERR_BAD_ARG, "split tube unit: sin / cos cache form");
+  if (g0 >= 3 && (lanes != 1 || DTMPC_FAST_F64)) return set_err(DTMPC_ERR_BAD_ARG, "split tube unit: sin / cos cache form");
   switch (M) {
 #ifdef DTMPC_FAST_M_ONLY
     ILP_CASE(DTMPC_FAST_M_ONLY)
@@ -3916,6 +4127,16 @@ int dtmpc_diag_tube_sincos_cache(int dtype, int32_t horizon, int64_t B, int64_t 
   sp.dbas_gamma = dbas_gamma;
   const int64_t cmax = dtmpc::tube_fast_chunk_max(horizon, lanes), c = chunk < cmax ? chunk : cmax;
   return dtmpc::tube_fast_scc(horizon, B, B < c ? B : c, lanes, dtmpc::fast_g0(&sp)) ? 1 : 0;
+}
+// diagnostics (not part of include/dtmpc.h): the stride of the sparse state rows when every launch of that step takes the
+// kernel with them (tube_fast_xs: the rule and its switch), else 0 (dense rows)
+int dtmpc_diag_tube_sparse_rows(int dtype, int32_t horizon, int64_t B, int64_t chunk, int32_t lanes, double dbas_gamma) {
+  if (dtype != DTMPC_F32 || horizon < 1 || B < 1 || chunk < 1 || (lanes != 1 && lanes != 2 && lanes != 4)) return 0;
+  dtmpc_spec sp;
+  std::memset(&sp, 0, sizeof(sp));
+  sp.dbas_gamma = dbas_gamma;
+  const int64_t cmax = dtmpc::tube_fast_chunk_max(horizon, lanes), c = chunk < cmax ? chunk : cmax;
+  return dtmpc::tube_fast_xs(horizon, B, B < c ? B : c, lanes, dtmpc::fast_g0(&sp));
 }
 // diagnostics (not part of include/dtmpc.h): the counter-calibration copy of record_stream_kernel over
 // src / dst buffers of (N+1) x 16 + N x 8 bytes per trajectory (< 2^31 bytes)

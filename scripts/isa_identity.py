@@ -1,0 +1,76 @@
+"""Device-code identity of two builds, kernel by kernel (the method of profiles/r08/isa_identity.txt): per unit the
+gfx950 code object is unbundled as build.py's _code_object does, disassembled with llvm-objdump -d --no-show-raw-insn
+--no-leading-addr and split per kernel; kernels are compared by their instruction text and by their metadata notes
+(register, spill and segment sizes).  Kernels present on one side only are listed, not compared.
+usage: isa_identity.py PARENT_product_objs.txt BRANCH_product_objs.txt   (build/obj/product_objs.txt of each build)"""
+import hashlib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ProcessPoolExecutor
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "differentiable-tube-mpc_amd"))
+import build as B  # noqa: E402
+
+NOTE = re.compile(r"\s+\.(name|vgpr_count|sgpr_count|agpr_count|vgpr_spill_count|sgpr_spill_count|"
+                  r"private_segment_fixed_size|group_segment_fixed_size|kernarg_segment_size):\s+(\S+)")
+
+
+def unit(obj):
+    with tempfile.TemporaryDirectory() as d:
+        co = B._code_object(obj, d)
+        dis = subprocess.run([f"{B.LLVM}/llvm-objdump", "-d", f"--mcpu={B.ARCH}", "--no-show-raw-insn",
+                              "--no-leading-addr", co], check=True, capture_output=True, text=True).stdout
+        notes = subprocess.run([f"{B.LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True,
+                               text=True).stdout
+    res, cur = {}, None
+    for line in notes.splitlines():
+        m = NOTE.match(line)
+        if m and m.group(1) == "name":
+            cur = res.setdefault(m.group(2), {})
+        elif m and cur is not None:
+            cur[m.group(1)] = m.group(2)
+    code, name = {}, None
+    for line in dis.splitlines():
+        m = re.match(r"^<?([_A-Za-z0-9.$]+)>?:\s*$", line)
+        if m:
+            name = m.group(1) if m.group(1) in res else None
+            continue
+        if name:
+            # without the trailing "// address: encoding" comment: kernels behind a new one move in the code object
+            code.setdefault(name, []).append(line.split("//")[0].strip())
+    return os.path.basename(obj).split(".")[0], {k: ("\n".join(v), res[k]) for k, v in code.items()}
+
+
+def main(pa, br):
+    objs = [open(p).read().split() for p in (pa, br)]
+    with ProcessPoolExecutor(max_workers=8) as pool:
+        P, Q = (dict(pool.map(unit, o)) for o in objs)
+    print("# unit  kernels(parent/branch)  sha256(common kernels' disassembly) parent  branch  resource notes  verdict")
+    ok = True
+    for tu in sorted(P):
+        a, b = P[tu], Q[tu]
+        common = sorted(set(a) & set(b))
+        ha, hb = (hashlib.sha256("\n".join(k + "\n" + s[k][0] for k in common).encode()).hexdigest()[:16] for s in (a, b))
+        notes = all(a[k][1] == b[k][1] for k in common)
+        same = ha == hb and notes
+        ok &= same
+        print(f"{tu:22s} {len(a):3d}/{len(b):3d}  {ha}  {hb}  {'equal' if notes else 'DIFFER'}  "
+              f"{'IDENTICAL' if same else 'DIFFERENT'}")
+        for k in sorted(set(b) - set(a)):
+            print(f"    new in branch: {k}  {b[k][1]}")
+        for k in sorted(set(a) - set(b)):
+            ok = False
+            print(f"    missing in branch: {k}")
+        if not same:
+            for k in common:
+                if a[k] != b[k]:
+                    print(f"    differs: {k}")
+    print("ALL COMMON KERNELS IDENTICAL" if ok else "DIFFERENCES")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1], sys.argv[2]))
