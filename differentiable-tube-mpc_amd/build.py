@@ -4,7 +4,7 @@ Plain hipcc, no build system: the translation units compiled in parallel, then l
 csrc/dtmpc_kernels.hip (paper path + per-function entry points), csrc/dtmpc_fast.hip (the fused tube step of
 the paper configuration), csrc/dtmpc_fast_ilqr.hip (its solver as the standalone batched iLQR), csrc/dtmpc_fast_general.hip (the
 general path's solves on it), csrc/dtmpc_fast_scenes.hip (both with per-trajectory scenes), csrc/dtmpc_fast_own.hip (the tube step with
-per-trajectory ancillary weights), csrc/dtmpc_general.hip (general IFT
+per-trajectory ancillary weights), csrc/dtmpc_fast_layer.hip (the differentiable solve's backward), csrc/dtmpc_general.hip (general IFT
 path), csrc/dtmpc_receding.hip (receding-horizon nominal MPC driver), csrc/dtmpc_control.hip (tanh-box
 control map + cost derivatives), csrc/dtmpc_ocp.hip (tape cost of core/ocp.py), csrc/dtmpc_systems.hip
 (per-point kernels of the reference's per-function API: dynamics, h, barriers, Jacobians, clamp, cost
@@ -21,7 +21,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", f)
         for f in ("dtmpc_kernels.hip", "dtmpc_fast.hip", "dtmpc_fast_ilp.hip", "dtmpc_fast64.hip", "dtmpc_fast64_ilp.hip",
-                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
+                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_fast_layer.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
                   "dtmpc_control.hip", "dtmpc_ocp.hip", "dtmpc_systems.hip")]
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("dtmpc_device.hpp", "dtmpc_solver.hpp", "dtmpc_general.hpp",
                                                  "dtmpc_host.hpp", "dtmpc_ls_pk.hpp")] + [
@@ -129,7 +129,7 @@ def build(force: bool = False, variant: str = "", defines=(), only=(), on_produc
             json.dump(rep, f, indent=1, sort_keys=True)
         bad = [(k, v["scratch"]) for r in rep.values() for k, v in r.items() if v.get("scratch", 0)]
         if bad and os.environ.get("DTMPC_RESOURCE_STRICT", "1") != "0":
-            raise RuntimeError("f64 fused kernels with a private segment (scratch): " +
+            raise RuntimeError("resource-checked fused kernels with a private segment (scratch): " +
                                ", ".join(f"{k} ({b} B)" for k, b in bad))
         # and no 128-bit record store of a fused kernel may have its data registers written inside its two wait
         # states (the store-data hazard, csrc/dtmpc_fast.hip st128; profiles/r05/store_hazard.txt)
@@ -177,7 +177,9 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # f64 fused units: every kernel must run without a private segment (round 5) -- the f64
 # defects of rounds 3-4 (wrong results, run-to-run differences, an illegal address) came only from f64 fused
 # kernels whose per-lane divergent loops spilled VGPRs to scratch or kept results in scratch through a pointer
-RESOURCE_CHECKED = ("dtmpc_fast64", "dtmpc_fast64_ilp", "dtmpc_fast64_ilqr", "dtmpc_fast64_general")
+# ... and the f32 solve-backward unit (dtmpc_fast_layer): its kernel holds a 4 x 4 recursion and twenty loaded-ahead
+# values per lane in unrolled local arrays, which must all be registers
+RESOURCE_CHECKED = ("dtmpc_fast64", "dtmpc_fast64_ilp", "dtmpc_fast64_ilqr", "dtmpc_fast64_general", "dtmpc_fast_layer")
 
 
 def kernel_resources(obj: str) -> dict:
@@ -484,7 +486,7 @@ def check_resources(objs, strict: bool = True) -> dict:
         report[tu] = res
         bad += [(tu, k, v["scratch"]) for k, v in res.items() if v.get("scratch", 0)]
     if bad and strict:
-        raise RuntimeError("f64 fused kernels with a private segment (scratch): " +
+        raise RuntimeError("resource-checked fused kernels with a private segment (scratch): " +
                            ", ".join(f"{k} ({s} B)" for _, k, s in bad))
     return report
 

@@ -30,7 +30,7 @@
 // this file is the tube step's translation unit; dtmpc_fast_ilqr.hip / dtmpc_fast_general.hip include it
 // for the standalone iLQR's and the general path's instantiations (their host parts below)
 #if defined(DTMPC_FAST_ILQR_TU) || defined(DTMPC_FAST_GENERAL_TU) || defined(DTMPC_FAST_ILP_TU) || \
-    defined(DTMPC_FAST_SCENES_TU) || defined(DTMPC_FAST_OWN_TU)
+    defined(DTMPC_FAST_SCENES_TU) || defined(DTMPC_FAST_OWN_TU) || defined(DTMPC_FAST_LAYER_TU)
 #define DTMPC_FAST_AUX_TU 1
 #endif
 // The one-lane tube kernels (the headline's form) and the f32 two-lane ones live in their own translation units
@@ -4027,6 +4027,10 @@ int launch_tube_fast_own(int M, int lanes, bool scene, dim3 grid, unsigned bs, h
 #undef OWN_LANES
 #undef OWN_LAUNCH
 }
+
+#elif defined(DTMPC_FAST_LAYER_TU)  // the differentiable solve's backward (csrc/dtmpc_fast_layer.hip), f32 only
+
+// (its kernel and host part follow this file in that unit: it takes the device functions above, no launcher here)
 
 #else  // the general path's solves (csrc/dtmpc_fast_general.hip)
 

@@ -242,6 +242,13 @@ PROTOTYPES = {
         [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcTubeCfg), I64, I64, I64, C.POINTER(DtmpcTubeState), P, P,
          C.POINTER(DtmpcOwnTheta)],
     ),
+    "dtmpc_solve_backward_supported": (I32, [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost)]),
+    "dtmpc_solve_backward_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64]),
+    "dtmpc_solve_backward": (
+        C.c_int,
+        [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), I64, P, P, P, P, P, P, P, P, P, P, P, P, C.c_size_t, P,
+         P],
+    ),
     "dtmpc_sensitivity_upper_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64]),
     "dtmpc_ddp_sensitivity_upper": (
         C.c_int,

@@ -16,6 +16,7 @@ from .ddp import (
     rollout,
 )
 from .ift import IFTGradient, IFTInputs, ift_gradient
+from .layer import SolveGradient, diff_ilqr_solve, solve_backward
 from .params import AuxiliaryTheta, NominalTheta, theta_from_raw
 from .problem import (
     AdaptConfig,
@@ -68,6 +69,9 @@ __all__ = [
     "PaperSetup",
     "QuadraticCost",
     "SensitivityResult",
+    "SolveGradient",
+    "diff_ilqr_solve",
+    "solve_backward",
     "TubeMPC",
     "allreduce_sums",
     "dbas_init",

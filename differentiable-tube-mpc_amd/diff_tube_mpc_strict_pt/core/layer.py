@@ -1,0 +1,273 @@
+"""The iLQR solve as a differentiable layer: ``loss(X*, V*).backward()`` reaches the cost weights, the target and
+the tracking references.
+
+What the gradient is.  ``solve_backward`` evaluates the reference's implicit-function gradient AT THE TAPE IT IS
+GIVEN: ddp_sensitivity (core/ddp.py:317-427 -- the backward pass with the active set of the box frozen, reg = 1e-9,
+the Gauss-Newton L_zz, i.e. no second derivatives of the dynamics) with the incoming ``grad_X`` / ``grad_V`` as the
+upper gradients, then ift_gradient's accumulation (core/ift.py:35-92) restricted to the plain weights Q, R, Qf, q_b
+and the references.  It is the quantity the paper's Algorithm 2 descends along.  It is the gradient of the solver's
+output only where the solve has converged: on a tape that is not a stationary point of the lower problem (an
+iteration cap, a failed line search) it is still well defined, but it is the sensitivity of the KKT system
+linearised there, not of the iterate.  Gradients w.r.t. x0, the warm start, the obstacle geometry and the DBaS
+parameters (alpha, gamma, tightening) are not provided; the last remain ``ift_gradient``'s.
+
+Where ``dtmpc_solve_backward_supported`` says yes (f32, smooth-min, 1..8 obstacles, relaxed inverse barrier) the
+rows come from ONE launch of the fused kernel (csrc/dtmpc_fast_layer.hip), which writes no sensitivity tape;
+elsewhere (f64, min / single aggregation, log barrier) from ``dtmpc_ddp_sensitivity_upper`` and a few tensor
+operations."""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from .. import _abi, _lib
+from .ddp import (ILQRResult, _ddp_sensitivity_upper, _dtype_code, _ptr, _require_device, from_soa, ilqr_solve,
+                  raise_for_status, to_soa)
+from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, pack_scenes
+
+__all__ = ["SolveGradient", "solve_backward", "diff_ilqr_solve"]
+
+
+@dataclass(frozen=True)
+class SolveGradient:
+    """Per-trajectory rows of d loss / d (plain weights, references) at one tape."""
+
+    weights: Tensor            # [B, 9]: Q(3) R(2) Qf(3) qb
+    target: Optional[Tensor]   # [B, 3] (target cost)
+    X_ref: Optional[Tensor]    # [B, N+1, 3] (tracking cost)
+    U_ref: Optional[Tensor]    # [B, N, 2]
+    status: Tensor             # [B] int32, DTMPC_ST_NONFINITE where a row is not finite
+
+
+def _nonfinite_status(*rows: Optional[Tensor]) -> Tensor:
+    bad = None
+    for r in rows:
+        if r is None:
+            continue
+        b = ~torch.isfinite(r.reshape(r.shape[0], -1)).all(1)
+        bad = b if bad is None else bad | b
+    return bad.to(torch.int32) * _abi.ST_NONFINITE
+
+
+def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor, V: Tensor, grad_X: Tensor,
+                   grad_V: Tensor, X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
+                   scenes: Optional[Tensor] = None, check: bool = True) -> SolveGradient:
+    """The gradient of an upper loss w.r.t. the plain cost weights and the references, per trajectory, from the
+    loss's gradients ``grad_X`` [B, N+1, 4] / ``grad_V`` [B, N, 2] w.r.t. the tape (X [B, N+1, 4], V [B, N, 2]).
+
+    The reference's IFT at the given tape with the Gauss-Newton L_zz of ddp_sensitivity and the active set frozen
+    (see the module docstring): the gradient of the solver's output only where the solve has converged; the
+    quantity the paper's Algorithm 2 uses.
+
+    cost.kind 'track' needs X_ref [B, N+1, >=3] and U_ref [B, N, 2] and returns their gradient rows; 'target'
+    returns the target's.  scenes ([3M + 3, B], pack_scenes): trajectory i linearises with its own obstacles and a
+    target cost uses its own target (fused f32 kernel only).  check: raise FloatingPointError on a non-finite row
+    (else see ``status``)."""
+    if cost.wrap_angle:
+        raise ValueError("solve_backward: a cost with wrap_angle is not supported (the reference's sensitivity "
+                         "closures carry no wrapped heading error)")
+    _require_device(X, V, grad_X, grad_V, X_ref, U_ref, scenes)
+    B, N = X.shape[0], problem.horizon
+    if X.shape != (B, N + 1, 4) or V.shape != (B, N, 2):
+        raise ValueError(f"X must be [B, {N + 1}, 4] and V [B, {N}, 2]")
+    if grad_X.shape != (B, N + 1, 4) or grad_V.shape != (B, N, 2):
+        raise ValueError(f"grad_X must be [{B}, {N + 1}, 4] and grad_V [{B}, {N}, 2]")
+    track = cost.kind == "track"
+    if track and (X_ref is None or U_ref is None):
+        raise ValueError("the tracking cost needs X_ref and U_ref")
+    if not track and (X_ref is not None or U_ref is not None):
+        raise ValueError("X_ref / U_ref go with the tracking cost")
+    lib = _lib.load()
+    spec, cc = problem.to_c(), cost.to_c()
+    dt, dev = X.dtype, X.device
+    kw = dict(dtype=dt, device=dev)
+    if lib.dtmpc_solve_backward_supported(_dtype_code(X), C.byref(spec), C.byref(cc)):
+        if scenes is not None:
+            check_scenes(scenes, len(problem.obstacles), B, dt, dev)
+        Xs, Us, gx, gu = to_soa(X), to_soa(V.to(dt)), to_soa(grad_X.to(dt)), to_soa(grad_V.to(dt))
+        Xr = to_soa(X_ref[..., :3].to(dt)) if track else None
+        Ur = to_soa(U_ref.to(dt)) if track else None
+        gw = torch.empty(9, B, **kw)
+        gt = None if track else torch.empty(3, B, **kw)
+        gxr = torch.empty(N + 1, 3, B, **kw) if track else None
+        gur = torch.empty(N, 2, B, **kw) if track else None
+        wb = int(lib.dtmpc_solve_backward_workspace_bytes(_dtype_code(X), N, B))
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+        _lib.check(lib.dtmpc_solve_backward(_dtype_code(X), C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(),
+                                            _ptr(Xr), _ptr(Ur), _ptr(scenes), gx.data_ptr(), gu.data_ptr(),
+                                            gw.data_ptr(), _ptr(gt), _ptr(gxr), _ptr(gur), work.data_ptr(), wb,
+                                            status.data_ptr(), _lib.stream_of(X)), "dtmpc_solve_backward")
+        out = SolveGradient(weights=gw.t().contiguous(), target=None if track else gt.t().contiguous(),
+                            X_ref=from_soa(gxr) if track else None, U_ref=from_soa(gur) if track else None,
+                            status=status)
+    else:
+        if scenes is not None:
+            raise ValueError("solve_backward: per-trajectory scenes need the fused kernel "
+                             "(dtmpc_solve_backward_supported: f32, smooth-min, 1..8 obstacles, inverse barrier)")
+        if spec.h_offset != 0.0:
+            raise ValueError("solve_backward: a tightened h (h_offset) is not supported")
+        s = _ddp_sensitivity_upper(problem, cost, X, V, grad_X, grad_V, False, False)
+        dX, dV = s.delta_X, s.delta_V
+        Q = torch.tensor(cost.Q, **kw)
+        R = torch.tensor(cost.R, **kw)
+        Qf = torch.tensor(cost.Qf, **kw)
+        if track:
+            r, ub = X_ref[..., :3].to(dt), U_ref.to(dt)
+        else:
+            r = torch.tensor(cost.target, **kw).expand(B, N + 1, 3)
+            ub = torch.zeros(B, N, 2, **kw)
+        ex = X[..., :3] - r
+        gQ = (2.0 * ex[:, :N] * dX[:, :N, :3]).sum(1)
+        gR = (2.0 * (V.to(dt) - ub) * dV).sum(1)
+        gQf = 2.0 * ex[:, N] * dX[:, N, :3]
+        gqb = (2.0 * X[..., 3] * dX[..., 3]).sum(1, keepdim=True)
+        gxr = torch.cat([-2.0 * Q * dX[:, :N, :3], (-2.0 * Qf * dX[:, N, :3])[:, None]], 1)
+        gur = -2.0 * R * dV
+        gw = torch.cat([gQ, gR, gQf, gqb], 1)
+        gt = None if track else gxr.sum(1)
+        status = _nonfinite_status(gw, gt, gxr if track else None, gur if track else None, dX[:, N])
+        out = SolveGradient(weights=gw, target=gt, X_ref=gxr if track else None, U_ref=gur if track else None,
+                            status=status)
+    if check:
+        raise_for_status(out.status, "solve_backward")
+    return out
+
+
+class _Solve(torch.autograd.Function):
+    """X*, V* of a finished solve as functions of the weight / reference tensors: forward hands the tape through,
+    backward is solve_backward at that tape."""
+
+    @staticmethod
+    def forward(ctx, X, V, problem, cost, scenes, per_traj_target, nref, Q, R, Qf, qb, target, X_ref, U_ref):
+        ctx.problem, ctx.cost, ctx.scenes = problem, cost, scenes
+        ctx.per_traj_target, ctx.nref = per_traj_target, nref
+        ctx.shapes = tuple(None if t is None else (t.shape, t.dtype) for t in (Q, R, Qf, qb, target, X_ref, U_ref))
+        ctx.save_for_backward(X, V, *(t for t in (X_ref, U_ref) if t is not None))
+        ctx.flagged = None
+        return X.clone(), V.clone()
+
+    @staticmethod
+    def backward(ctx, gX, gV):
+        X, V, *refs = ctx.saved_tensors
+        Xr, Ur = (refs + [None, None])[:2]
+        gX = torch.zeros_like(X) if gX is None else gX
+        gV = torch.zeros_like(V) if gV is None else gV
+        g = solve_backward(problem=ctx.problem, cost=ctx.cost, X=X, V=V, grad_X=gX.contiguous(),
+                           grad_V=gV.contiguous(), X_ref=None if Xr is None else Xr.detach(),
+                           U_ref=None if Ur is None else Ur.detach(), scenes=ctx.scenes, check=False)
+        keep = (g.status == 0)
+        ctx.flagged = g.status  # [B] int32: the trajectories left out of this backward
+
+        def rows(t):  # flagged trajectories contribute zero rows (where, not a product: their rows may hold NaN)
+            return None if t is None else torch.where(keep.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros_like(t))
+
+        w = rows(g.weights)
+        ws = w.sum(0)
+        out = [None] * 7
+        need = ctx.needs_input_grad[7:]
+        sh = ctx.shapes
+        for j, sl in enumerate((slice(0, 3), slice(3, 5), slice(5, 8), slice(8, 9))):
+            if sh[j] is not None and need[j]:
+                out[j] = ws[sl].reshape(sh[j][0]).to(sh[j][1])
+        if sh[4] is not None and need[4] and g.target is not None:
+            t = rows(g.target)
+            out[4] = (t if ctx.per_traj_target else t.sum(0)).reshape(sh[4][0]).to(sh[4][1])
+        if sh[5] is not None and need[5] and g.X_ref is not None:
+            gx = rows(g.X_ref)
+            if ctx.nref > 3:  # the solver reads three columns of X_ref: the others get zeros
+                gx = torch.cat([gx, gx.new_zeros(*gx.shape[:2], ctx.nref - 3)], 2)
+            out[5] = gx.to(sh[5][1])
+        if sh[6] is not None and need[6] and g.U_ref is not None:
+            out[6] = rows(g.U_ref).to(sh[6][1])
+        return (None,) * 7 + tuple(out)
+
+
+@dataclass(frozen=True)
+class DiffILQRResult(ILQRResult):
+    """ILQRResult whose X / V carry a grad_fn; ``backward_status()`` gives the last backward's per-trajectory
+    status ([B] int32, None before any backward): non-zero trajectories contributed zero rows."""
+
+    _node: object = None
+
+    def backward_status(self) -> Optional[Tensor]:
+        return getattr(self._node, "flagged", None)
+
+
+def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q: Tensor, R: Tensor, Qf: Tensor,
+                    qb: Tensor, x0: Tensor, V_init: Tensor, target: Optional[Tensor] = None,
+                    X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
+                    obstacles: Optional[Tensor] = None, lanes: int = 0, check: bool = True) -> ILQRResult:
+    """``ilqr_solve`` whose X* / V* are differentiable w.r.t. Q [3], R [2], Qf [3], qb [], the target ([3] shared
+    or [B, 3] per trajectory; kind 'target') and X_ref [B, N+1, >=3] / U_ref [B, N, 2] (kind 'track').
+
+    Forward is exactly ``ilqr_solve`` (the same kernels, bitwise the same X*, V*): with a [B, 3] target or
+    ``obstacles`` [B, M, 3] it runs ``ilqr_solve(..., scenes=pack_scenes(...))``.  The QuadraticCost is built from
+    the weight tensors' VALUES -- host doubles in the ABI -- so every call makes one device-to-host read of the
+    nine weights (and of a shared target): it synchronises the stream.
+
+    Backward is ``solve_backward`` at the returned tape with the incoming gradients (a missing one is zeros): the
+    reference's IFT with the Gauss-Newton L_zz of ddp_sensitivity and the active set frozen -- the gradient of the
+    solver's output only where the solve has converged, the quantity the paper's Algorithm 2 uses.  Shared tensors
+    (Q, R, Qf, qb, a [3] target) receive the sum of the per-trajectory rows, a [B, 3] target and the references
+    their rows; a fourth column of X_ref gets zeros.  A trajectory whose backward is flagged (non-finite row)
+    contributes zero rows; ``result.backward_status()`` holds the flags of the last backward.  The same tensor
+    passed twice (say as Q and Qf) accumulates both gradients, as autograd does.
+
+    Refused: gradients w.r.t. x0 and V_init (the reference detaches xi, and the warm start is not an argument of
+    the optimum), w.r.t. obstacles, a wrapped heading error, and DBaS parameters as tensors (their gradients remain
+    ``ift_gradient``'s).  check: the forward raises as ``ilqr_solve`` does."""
+    if kind not in ("target", "track"):
+        raise ValueError(f"unknown cost kind {kind!r}")
+    if x0.requires_grad or V_init.requires_grad:
+        raise ValueError("diff_ilqr_solve: no gradient w.r.t. x0 or V_init -- the reference's IFT detaches the "
+                         "initial state (xi), and the warm start is not an argument of the optimum; detach them")
+    if obstacles is not None and isinstance(obstacles, Tensor) and obstacles.requires_grad:
+        raise ValueError("diff_ilqr_solve: no gradient w.r.t. the obstacle geometry; detach obstacles")
+    for name in ("dbas_alpha", "dbas_gamma", "dbas_eps", "obs_beta"):
+        if isinstance(getattr(problem, name), Tensor):
+            raise ValueError(f"diff_ilqr_solve: problem.{name} must be a float -- gradients w.r.t. the DBaS "
+                             "parameters remain ift_gradient's")
+    _require_device(x0, V_init, Q, R, Qf, qb, target, X_ref, U_ref,
+                    obstacles if isinstance(obstacles, Tensor) else None)
+    B, N = x0.shape[0], problem.horizon
+    track = kind == "track"
+    if track and (X_ref is None or U_ref is None):
+        raise ValueError("kind 'track' needs X_ref and U_ref")
+    if track and target is not None:
+        raise ValueError("target goes with kind 'target'")
+    if not track and (X_ref is not None or U_ref is not None):
+        raise ValueError("X_ref / U_ref go with kind 'track'")
+    if not track and target is None:
+        raise ValueError("kind 'target' needs target ([3] or [B, 3])")
+    if Q.shape != (3,) or R.shape != (2,) or Qf.shape != (3,) or qb.numel() != 1:
+        raise ValueError("Q [3], R [2], Qf [3], qb [] (shared weights)")
+    per_traj = (not track) and target.dim() == 2
+    if not track and tuple(target.shape) not in ((3,), (B, 3)):
+        raise ValueError(f"target must be [3] or [{B}, 3]")
+    # one device-to-host read: the ABI's cost weights are host doubles
+    host = torch.cat([t.detach().reshape(-1).to(torch.float64) for t in
+                      (Q, R, Qf, qb) + ((target,) if (not track and not per_traj) else ())]).cpu().tolist()
+    cost = QuadraticCost(kind=kind, Q=tuple(host[0:3]), R=tuple(host[3:5]), Qf=tuple(host[5:8]), qb=host[8],
+                         target=tuple(host[9:12]) if len(host) > 9 else (0.0, 0.0, 0.0))
+    scenes = None
+    if per_traj or obstacles is not None:
+        obs = obstacles
+        if obs is None:
+            obs = torch.tensor([[o.center[0], o.center[1], o.radius] for o in problem.obstacles],
+                               dtype=torch.float64).expand(B, -1, 3)
+        tg = target.detach() if per_traj else (torch.tensor(cost.target, dtype=torch.float64).expand(B, 3))
+        scenes = pack_scenes(problem, obs, tg, dtype=x0.dtype, device=x0.device)
+    res = ilqr_solve(problem=problem, cost=cost, cfg=cfg, x0=x0, V_init=V_init,
+                     X_ref=None if X_ref is None else X_ref.detach(), U_ref=None if U_ref is None else U_ref.detach(),
+                     check=check, debug_name="diff_ilqr_solve", lanes=lanes, scenes=scenes)
+    nref = 0 if X_ref is None else X_ref.shape[-1]
+    Xd, Vd = _Solve.apply(res.X, res.V, problem, cost, scenes, per_traj, nref, Q, R, Qf, qb, target, X_ref, U_ref)
+    fields = {f.name: getattr(res, f.name) for f in dataclasses.fields(ILQRResult)}
+    fields.update(X=Xd, V=Vd)
+    return DiffILQRResult(**fields, _node=Xd.grad_fn)

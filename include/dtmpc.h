@@ -437,6 +437,43 @@ int dtmpc_tube_step_own(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg*
                         int64_t global_offset, int64_t step, const dtmpc_tube_state* state,
                         const void* w, void* stream, const dtmpc_own_theta* own);
 
+/* ---- differentiable solve: the backward of dtmpc_ilqr_solve --------------------------------- */
+/*
+ * Given a solve's tape (X, U) and the gradients gX, gU of an upper loss w.r.t. that tape, the gradient of the loss
+ * w.r.t. the PLAIN cost weights and the references, per trajectory, in one launch: the reference's ddp_sensitivity
+ * (core/ddp.py:317-427: backward pass with the active set, reg = 1e-9, _solve_reduced, upper gradients as given)
+ * and its forward pass fused with the accumulation of ift_gradient (core/ift.py:35-92) restricted to those
+ * parameters -- none of whose terms involves delta_lambda, so no sensitivity tape is written:
+ *   g_w rows Q(3) R(2) Qf(3) qb:  g_Q[i] = sum_{k<N} 2 (x_k[i] - r_k[i]) dx_k[i],  g_R[j] = sum_{k<N} 2 (u_k[j] -
+ *   ubar_k[j]) du_k[j],  g_Qf[i] = 2 (x_N[i] - r_N[i]) dx_N[i],  g_qb = sum_{k<=N} 2 b_k db_k;
+ *   g_xref[k][i] = -2 Q_i dx_k[i] (Qf_i at k = N),  g_uref[k][j] = -2 R_j du_k[j];
+ *   g_target[i] = sum_k g_xref[k][i] with r_k = target, ubar = 0.
+ * It is the reference's IFT at the given tape (Gauss-Newton L_zz, active set frozen): the gradient of the solver's
+ * output only where the solve has converged.  Gradients w.r.t. the DBaS parameters remain dtmpc_ift_gradient's.
+ * Added beside ABI 8 (csrc/dtmpc_fast_layer.hip); discovered through dtmpc_solve_backward_supported. */
+
+/* 1 for DTMPC_F32, smooth-min aggregation over 1..8 obstacles, the relaxed inverse barrier, h_offset == 0 and an
+ * unwrapped cost (any dbas_gamma); else 0.  Host-only. */
+int32_t dtmpc_solve_backward_supported(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost);
+
+/* Scratch bytes of dtmpc_solve_backward: the gains and the linearisation, horizon x 80 B per trajectory in f32
+ * (0 for another dtype, horizon < 1 or B < 1). */
+size_t dtmpc_solve_backward_workspace_bytes(int dtype, int32_t horizon, int64_t B);
+
+/* X [N+1][4][B], U [N][2][B]: the tape.  Xref [N+1][3][B], Uref [N][2][B]: DTMPC_COST_TRACK only, else NULL.
+ * scenes [3M+3][B] or NULL (dtmpc_tube_state.scenes' layout): trajectory i linearises with its own obstacles and a
+ * DTMPC_COST_TARGET cost uses its own target.  gX [N+1][4][B] (row N = the gradient w.r.t. x_N), gU [N][2][B].
+ * g_w [9][B]; g_target [3][B] or NULL (target cost only); g_xref [N+1][3][B], g_uref [N][2][B] or NULL (tracking
+ * cost only).  status [B]: DTMPC_ST_NONFINITE is OR-ed into trajectory i's word when its dx_N or one of its output
+ * rows is non-finite; the other trajectories are untouched.  DTMPC_ERR_BAD_ARG, before any device call, for a NULL
+ * required pointer, B < 1, horizon < 1, work_bytes below dtmpc_solve_backward_workspace_bytes, a reference or
+ * reference-gradient pointer with a target cost, g_target with a tracking cost, or a configuration
+ * dtmpc_solve_backward_supported rejects. */
+int dtmpc_solve_backward(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
+                         const void* X, const void* U, const void* Xref, const void* Uref, const void* scenes,
+                         const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
+                         void* work, size_t work_bytes, int32_t* status, void* stream);
+
 
 /* ---- general (softplus / tanh parameterised) IFT path ------------------------------------ */
 /*

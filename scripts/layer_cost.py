@@ -1,0 +1,140 @@
+"""What the differentiable solve costs: the fused dtmpc_solve_backward against the composition that produces the same
+rows (dtmpc_ddp_sensitivity_upper, which writes the dX / dU tapes, plus the accumulation of core/ift.py:35-92 as
+tensor operations), same process, runs alternated; then forward and backward of diff_ilqr_solve.
+
+  python scripts/layer_cost.py [--batch 65536] [--rounds 5] [--reps 20] [--out FILE]
+
+B = 65,536, N = 50, M = 5, f32, the paper's target cost and ten iLQR iterations; the tape is the solve's own result
+and the upper gradients are seeded normals.  Both backward variants run on SoA buffers made once (no layout copies
+in the timed region); each figure is the median over `reps` calls between device events after a warm-up of 3, the
+spread max - min of the per-round medians.  `layer_forward` / `layer_backward` time diff_ilqr_solve(...) and
+loss.backward() as a user calls them (layout copies, the weights' device-to-host read and autograd included).  The
+bytes the fused kernel moves by construction are printed beside the times.  One JSON line."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "differentiable-tube-mpc_amd")]
+import torch  # noqa: E402
+
+from diff_tube_mpc_strict_pt import _abi, _lib  # noqa: E402
+from diff_tube_mpc_strict_pt.core import dbas_init, diff_ilqr_solve, ilqr_solve  # noqa: E402
+from diff_tube_mpc_strict_pt.core.ddp import to_soa  # noqa: E402
+from diff_tube_mpc_strict_pt.core.problem import paper_config, paper_setup_from_config  # noqa: E402
+
+
+def timed(fn, reps):
+    for _ in range(3):
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return statistics.median(a.elapsed_time(b) for a, b in ev)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a HIP device"
+    dev = torch.device("cuda", 0)
+    st = paper_setup_from_config(paper_config())
+    prob, cost, cfg = st.problem, st.nominal_cost, st.ilqr_nom
+    B, N = a.batch, prob.horizon
+    f32 = torch.float32
+    g = torch.Generator().manual_seed(1)
+    x = torch.stack([torch.rand(B, generator=g), torch.rand(B, generator=g), torch.rand(B, generator=g) * 1.5], 1).to(dev)
+    x0 = torch.cat([x, dbas_init(prob, x)[:, None]], 1)
+    V0 = torch.zeros(B, N, 2, device=dev)
+    res = ilqr_solve(problem=prob, cost=cost, cfg=cfg, x0=x0, V_init=V0, check=False)
+    gX = torch.randn(B, N + 1, 4, generator=g).to(dev)
+    gU = torch.randn(B, N, 2, generator=g).to(dev)
+    lib = _lib.load()
+    spec, cc = prob.to_c(), cost.to_c()
+    Xs, Us, gx, gu = to_soa(res.X), to_soa(res.V), to_soa(gX), to_soa(gU)
+    kw = dict(dtype=f32, device=dev)
+    gw, gt = torch.empty(9, B, **kw), torch.empty(3, B, **kw)
+    wb = lib.dtmpc_solve_backward_workspace_bytes(_abi.F32, N, B)
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    stream = _lib.stream_of(Xs)
+
+    def fused():
+        _lib.check(lib.dtmpc_solve_backward(_abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), None,
+                                            None, None, gx.data_ptr(), gu.data_ptr(), gw.data_ptr(), gt.data_ptr(),
+                                            None, None, work.data_ptr(), wb, status.data_ptr(), stream),
+                   "dtmpc_solve_backward")
+
+    dX, dU = torch.empty(N + 1, 4, B, **kw), torch.empty(N, 2, B, **kw)
+    work2 = torch.empty(lib.dtmpc_sensitivity_upper_workspace_bytes(_abi.F32, N, B), dtype=torch.uint8, device=dev)
+    tg = torch.tensor(cost.target, **kw).view(1, 3, 1)
+    Qw, Qfw = torch.tensor(cost.Q, **kw).view(1, 3, 1), torch.tensor(cost.Qf, **kw).view(3, 1)
+    comp = {}
+
+    def composition():
+        _lib.check(lib.dtmpc_ddp_sensitivity_upper(_abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(),
+                                                   gx.data_ptr(), gu.data_ptr(), dX.data_ptr(), dU.data_ptr(), None,
+                                                   work2.data_ptr(), status.data_ptr(), stream),
+                   "dtmpc_ddp_sensitivity_upper")
+        ex = Xs[:, :3] - tg
+        gQ = (2 * ex[:N] * dX[:N, :3]).sum(0)
+        gR = (2 * Us * dU).sum(0)
+        gQf = 2 * ex[N] * dX[N, :3]
+        gqb = (2 * Xs[:, 3] * dX[:, 3]).sum(0, keepdim=True)
+        comp["gw"] = torch.cat([gQ, gR, gQf, gqb], 0)
+        comp["gt"] = (-2 * Qw * dX[:N, :3]).sum(0) + -2 * Qfw * dX[N, :3]
+
+    Q, R, Qf, qb = (torch.tensor(v, device=dev, requires_grad=True) for v in (cost.Q, cost.R, cost.Qf, cost.qb))
+    tgt = torch.tensor(cost.target, device=dev, requires_grad=True)
+    hold = {}
+
+    def layer_forward():
+        hold["res"] = diff_ilqr_solve(problem=prob, cfg=cfg, kind="target", Q=Q, R=R, Qf=Qf, qb=qb, x0=x0, V_init=V0,
+                                      target=tgt, check=False)
+
+    def layer_backward():
+        r = hold["res"]
+        ((r.X * gX).sum() + (r.V * gU).sum()).backward(retain_graph=True)
+
+    ms = {k: [] for k in ("fused", "composition", "layer_forward", "layer_backward")}
+    for _ in range(a.rounds):
+        ms["fused"].append(timed(fused, a.reps))
+        ms["composition"].append(timed(composition, a.reps))
+        ms["layer_forward"].append(timed(layer_forward, max(a.reps // 4, 3)))
+        ms["layer_backward"].append(timed(layer_backward, max(a.reps // 4, 3)))
+    fused()
+    composition()
+    torch.cuda.synchronize()
+    ok = status == 0
+    err = float(((gw - comp["gw"]).abs().amax(0) / comp["gw"].abs().amax(0).clamp_min(1.0))[ok].max())
+    # target cost: backward reads X (three fields) 12, U 8, gX 16, gU 8 and writes the 80 B record; forward reads the
+    # record and X 16, U 8
+    per_step = 44 + 80 + 80 + 24
+    rec = {"B": B, "N": N, "M": len(prob.obstacles), "rounds": a.rounds, "reps": a.reps,
+           "bytes_per_traj_step_by_construction": per_step,
+           "bytes_per_launch_by_construction": per_step * N * B + (16 + 16 + 48) * B,
+           "flagged": int((~ok).sum()), "fused_vs_composition_max_rel": err}
+    for n, v in ms.items():
+        rec[n] = {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                  "spread": round(max(v) - min(v), 4)}
+    rec["fused_GBps_by_construction"] = round(rec["bytes_per_launch_by_construction"] / rec["fused"]["ms_median"] / 1e6, 1)
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
