@@ -2099,6 +2099,12 @@ __device__ __forceinline__ int line_search(const FP& p, const FCost& c, const FI
 }
 
 constexpr int kCmLead = 2;  // the commit's prefetch lead in steps (below)
+// ... and of its sparse-rows loop (SV::xs > 0): a build-time choice, so that variant libraries can be built for the
+// A/B (build.py --variant NAME -D DTMPC_CM_LEAD=n --only dtmpc_fast_ilp; profiles/r11/ab_commit_lead.txt)
+#ifndef DTMPC_CM_LEAD
+#define DTMPC_CM_LEAD 3
+#endif
+constexpr int kCmLeadSparse = DTMPC_CM_LEAD;
 // materialise the chosen candidate in place (commit_candidate): same arithmetic as its lane of the
 // line search; the old X[k+1] is read (prefetched) before it is overwritten
 template <bool TRACK, int M, class SV>
@@ -2154,19 +2160,47 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
     // compiler wait for the shorter path's count and cut the prefetch lead on the others.  RB buffers in rotation,
     // each refilled LEAD steps before use (LEAD + 1 of them live at a time).  Row N, where it is no multiple of XS,
     // is stored after the loop.  The loop is entered with the outstanding vector-memory operations its back edge
-    // carries -- (refill, U store), (refill, U store, X store) -- by rewriting X row 0 with x0, the value it holds,
-    // between and after the preloads.
-    constexpr int XS = SV::xs, LEAD = kCmLead, RB = (LEAD + XS) / XS * XS;
-    static_assert(LEAD == 2 && RB > LEAD && RB % XS == 0, "the entry sequence below is written for two steps of lead");
+    // carries: the body's last LEAD steps each leave (refill, U store) and, where the step ends a group, the group's X
+    // store.  So preload i stands for the refill of body step RB - LEAD + i and is followed by rewrites of X row 0 with
+    // x0, the value it holds, in the places of that step's stores (LEAD = 2: (refill, U store), (refill, U store, X
+    // store)).
+    constexpr int XS = SV::xs, LEAD = kCmLeadSparse, RB = (LEAD + XS) / XS * XS;
+    static_assert(LEAD >= 1 && RB > LEAD && RB % XS == 0, "LEAD + 1 live step buffers in a ring of whole groups");
     const int N1 = N - 1;
     auto ix = [&](int j) { return uidx(j < N1 ? j : N1); };
     const f4 X0v = f4{x0[0], x0[1], x0[2], x0[3]};
-    StepIn Bf[RB];
-    load_step<false, LX>(Bf[0], T0, ix(0));
-    rst2(S.r, S.XA, 0, 0, f2{X0v.x, X0v.y});
-    load_step<false, LX>(Bf[1], T0, ix(1));
-    rst2(S.r, S.XA, 0, 0, f2{X0v.x, X0v.y});
-    S.stx(0, X0v);
+    // A buffer is the three loads as they come (U row, the gain record's two quads); the step's Ka, Kb, kk are taken
+    // from them where the step runs.  Carried over the back edge as load_step's StepIn, Ka = (g0.xyz, 0) is a new
+    // vector made of the first quad: the compiler makes it by a copy of the quad, places the copies of the loop-carried
+    // buffers at the latch and waits there for every refill but the newest, whatever the lead
+    // (profiles/r11/commit_waits.txt).
+    static_assert(CMR && !LX, "the sparse-rows commit re-rolls the old tape and reads the gamma = 0 records");
+    struct Raw {
+      f2 V;
+      f4 g0, g1;
+    };
+    auto refill = [&](Raw& b, int kr) {
+      b.V = T0.u(kr);
+      b.g0 = rld4(T0.r, T0.G.K, kr, 0);
+      b.g1 = rld4(T0.r, T0.G.K, kr, 16 * ES);
+    };
+    auto cstep = [&](const Raw& b, int ks) {
+      StepIn c;
+      c.X0 = c.X1 = c.X2 = c.X3 = c.r0 = c.r1 = c.r2 = c.q0 = c.q1 = 0.f;
+      c.V0 = b.V.x;
+      c.V1 = b.V.y;
+      c.Ka = f4{b.g0.x, b.g0.y, b.g0.z, 0.f};  // Gains::load<true>
+      c.Kb = f4{b.g0.w, b.g1.x, b.g1.y, 0.f};
+      c.kk = f2{b.g1.z, b.g1.w};
+      step(c, ks);
+    };
+    Raw Bf[RB];
+#pragma unroll
+    for (int i = 0; i < LEAD; ++i) {
+      refill(Bf[i], ix(i));
+      rst2(S.r, S.XA, 0, 0, f2{X0v.x, X0v.y});
+      if ((RB - LEAD + i + 1) % XS == 0) S.stx(0, X0v);
+    }
     // whole groups in the loop, without a way out of its body: an early exit inside it reaches the loop header again
     // through the latch (the compiler gives a loop one exit), and the header's wait counts are then merged with that
     // path's shorter queue -- the dense form's loop waits for all but its newest refill in the first step of each trip
@@ -2174,8 +2208,8 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
     for (; k + RB <= N; k += RB) {
 #pragma unroll
       for (int j = 0; j < RB; ++j) {
-        load_step<false, LX>(Bf[(j + LEAD) % RB], T0, ix(k + j + LEAD));
-        step(Bf[j], k + j);
+        refill(Bf[(j + LEAD) % RB], ix(k + j + LEAD));
+        cstep(Bf[j], k + j);
         if ((j + 1) % XS == 0) S.stx(k + j + 1, f4{s0, s1, s2, sb});
       }
     }
@@ -2183,8 +2217,8 @@ __device__ __forceinline__ void commit(const FP& p, real al, const real* x0, rea
 #pragma unroll
     for (int j = 0; j < RB - 1; ++j) {
       if (k + j >= N) break;
-      load_step<false, LX>(Bf[(j + LEAD) % RB], T0, ix(k + j + LEAD));
-      step(Bf[j], k + j);
+      refill(Bf[(j + LEAD) % RB], ix(k + j + LEAD));
+      cstep(Bf[j], k + j);
       if ((j + 1) % XS == 0) S.stx(k + j + 1, f4{s0, s1, s2, sb});
     }
     if (N % XS != 0) S.stx(N, f4{s0, s1, s2, sb});
