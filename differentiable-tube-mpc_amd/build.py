@@ -24,7 +24,8 @@ SRCS = [os.path.join(HERE, "csrc", f)
                   "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_fast_layer.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
                   "dtmpc_control.hip", "dtmpc_ocp.hip", "dtmpc_systems.hip")]
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("dtmpc_device.hpp", "dtmpc_solver.hpp", "dtmpc_general.hpp",
-                                                 "dtmpc_host.hpp", "dtmpc_ls_pk.hpp")] + [
+                                                 "dtmpc_host.hpp", "dtmpc_ls_pk.hpp",
+                                                 "dtmpc_fast_layer_body.hpp")] + [
     os.path.join(os.path.dirname(HERE), "include", h) for h in ("dtmpc.h", "dtmpc_control.h", "dtmpc_systems.h")
 ]
 OUT = os.path.join(HERE, "diff_tube_mpc_strict_pt", "libdtmpc.so")
@@ -178,7 +179,8 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # defects of rounds 3-4 (wrong results, run-to-run differences, an illegal address) came only from f64 fused
 # kernels whose per-lane divergent loops spilled VGPRs to scratch or kept results in scratch through a pointer
 # ... and the f32 solve-backward unit (dtmpc_fast_layer): its kernel holds a 4 x 4 recursion and twenty loaded-ahead
-# values per lane in unrolled local arrays, which must all be registers
+# values per lane in unrolled local arrays, which must all be registers (its GEOM variants, dtmpc_solve_backward_geom,
+# hold 3M obstacle-row sums on top: profiles/r12/layer_geom_resources.txt)
 RESOURCE_CHECKED = ("dtmpc_fast64", "dtmpc_fast64_ilp", "dtmpc_fast64_ilqr", "dtmpc_fast64_general", "dtmpc_fast_layer")
 
 

@@ -19,6 +19,10 @@
 // choice; recomputing it in the forward sweep (sin / cos, h_grad, B': ~120 instructions against 80 B) is unmeasured.
 // The device functions are dtmpc_fast.hip's (h_grad, dbarrier, jac, vsincos, scene_p, scene_tg, pin_p) and
 // dtmpc_device.hpp / dtmpc_solver.hpp's (sens_qblocks, lu2, solve_reduced); nothing is restated here.
+// GEOM variant (dtmpc_solve_backward_geom, solve_backward_geom_kernel): the two terms that DO involve delta_lambda, the
+// rows w.r.t. the start state (g_x0 = tilde V_x[0]) and the obstacle circles.  It keeps the barrier row of V_xx and of
+// tilde V_x per step as well (25 values, 100 B), forms lam_k in the forward sweep and accumulates 3M sums (geom_row).
+// Both kernels include one body text, dtmpc_fast_layer_body.hpp.
 #define DTMPC_FAST_LAYER_TU 1
 #include "dtmpc_fast.hip"
 
@@ -26,6 +30,7 @@ namespace dtmpc {
 namespace fk {
 
 constexpr int kLayerRec = 20;  // workspace values per step: K (8), k_ff (2), a02 a12 a30 a31 a32 b00 b10 b30 b31, mask
+constexpr int kGeomRec = 25;   // GEOM: and the barrier row of V_xx (4) and of tilde V_x (1), what lam_k is formed from
 
 struct LArgs {
   int B;
@@ -56,229 +61,69 @@ struct LBwdIn {
 struct LFwdIn {
   real K[8], kf[2], A[9], act, x[4], u[2], r[3], q[2];
 };
+struct LFwdInG : LFwdIn {  // GEOM
+  real L[5];  // V_xx[k][3][0..3], tilde V_x[k][3]
+};
+// GEOM (dtmpc_solve_backward_geom): the kernel's block and two more outputs
+struct LKG {
+  LK k;       // p first
+  real* gx0;  // [4][B] or NULL
+  real* gob;  // [3M][B] or NULL: rows cx[0..M), cy[0..M), r2[0..M)
+};
+
+// One tape row's part of the obstacle rows: acc[j], acc[M + j], acc[2M + j] += co * B'(h(x)) * w_j(x) * (-2 (px - cx_j),
+// -2 (py - cy_j), -1), w_j = softmax_j(-beta h_j).  The weights and h are h_grad<M>'s (dtmpc_fast.hip) operation for
+// operation -- the same differences, exp2 arguments, sum order and reciprocal, so B' is evaluated at bitwise the h that
+// jac's linearisation saw -- with the terms kept apart instead of summed into grad h.
+template <int M>
+__device__ __forceinline__ void geom_row(const FP& p, real px, real py, real co, real (&acc)[3 * M]) {
+#pragma clang fp contract(off)
+  real hh[M], dxs[M], dys[M], zmax = 0.f;
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    const real dx = px - ocx<M>(p, i);
+    const real dy = py - ocy<M>(p, i);
+    const real h = dx * dx + dy * dy - or2<M>(p, i);
+    const real zi = p.neg_beta * h;
+    dxs[i] = dx;
+    dys[i] = dy;
+    hh[i] = h;
+    zmax = (i == 0 || zi > zmax) ? zi : zmax;
+  }
+  const real zl = zmax * real(1.44269504088896341);
+  real e[M], se = 0.f;
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(hh[i], p.nbl2e, -zl));
+    se += e[i];
+  }
+  const real inv = frcp(se);
+  const real hv = p.neg_inv_beta * (zmax + m_log(se));
+  const real s = (co * dbarrier(p, hv)) * inv;
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    const real cw = s * e[i];
+    acc[i] += cw * (-2.f * dxs[i]);
+    acc[M + i] += cw * (-2.f * dys[i]);
+    acc[2 * M + i] -= cw;
+  }
+}
 
 template <int M, bool TRACK>
 __global__ void __launch_bounds__(kBlock) solve_backward_kernel(LK kk) {
-  const LArgs& a = kk.a;
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (i >= a.B) return;
-  const size_t nb = (size_t)a.B;
-  FP p = kk.p;
-  FCost c = kk.c;
-  if (a.sc) {  // per-trajectory scene: this trajectory's obstacles and, for the target cost, its target
-    p = scene_p<M>(p, a.sc, nb, i);
-    if (!TRACK) c.tg = scene_tg<M>(a.sc, nb, i);
-  }
-  p = pin_p<M>(p);
-  const int N = p.N;
-  const real* X = a.X + i;
-  const real* U = a.U + i;
-  const real* GX = a.gX + i;
-  const real* GU = a.gU + i;
-  real* W = a.work + i;
-  const real lxx[4] = {2.f * c.Q0, 2.f * c.Q1, 2.f * c.Q2, 2.f * c.qb};
-  const real luu[2] = {2.f * c.R0, 2.f * c.R1};
-  const real pxx[4] = {2.f * c.Qf0, 2.f * c.Qf1, 2.f * c.Qf2, 2.f * c.qb};
-  const real reg = 1e-9f;
-  Riccati<real> R;  // R.Vx holds tilde V_x
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) R.Vxx[r][j] = r == j ? pxx[r] : 0.f;
-    R.Vx[r] = GX[(size_t)(4 * N + r) * nb];
-  }
-  real gxn, gyn, dBn;
-  dBn = dbarrier(p, h_grad<M>(p, X[(size_t)(4 * N) * nb], X[(size_t)(4 * N + 1) * nb], gxn, gyn));
-  auto bload = [&](LBwdIn& L, int k) {
-    L.x0 = X[(size_t)(4 * k) * nb];
-    L.x1 = X[(size_t)(4 * k + 1) * nb];
-    L.x2 = X[(size_t)(4 * k + 2) * nb];
-    L.u0 = U[(size_t)(2 * k) * nb];
-    L.u1 = U[(size_t)(2 * k + 1) * nb];
-    L.g0 = GX[(size_t)(4 * k) * nb];
-    L.g1 = GX[(size_t)(4 * k + 1) * nb];
-    L.g2 = GX[(size_t)(4 * k + 2) * nb];
-    L.g3 = GX[(size_t)(4 * k + 3) * nb];
-    L.h0 = GU[(size_t)(2 * k) * nb];
-    L.h1 = GU[(size_t)(2 * k + 1) * nb];
-  };
-  LBwdIn Bn;
-  bload(Bn, N - 1);
-  for (int k = N - 1; k >= 0; --k) {
-    const LBwdIn L = Bn;
-    if (k > 0) bload(Bn, k - 1);
-    real sn, cs;
-    vsincos(L.x2, sn, cs);
-    real gxk, gyk;
-    const real dBk = dbarrier(p, h_grad<M>(p, L.x0, L.x1, gxk, gyk));
-    const Jac<real> J = jac(p, sn, cs, L.u0, gxk, gyk, dBk, gxn, gyn, dBn);
-    gxn = gxk;
-    gyn = gyk;
-    dBn = dBk;
-    real Qxx[4][4], Qxu[4][2], Qux[2][4], Quu[2][2];
-    sens_qblocks(J, R.Vxx, lxx, luu, Qxx, Qxu, Qux, Quu);
-    const real* tv = R.Vx;
-    // tilde Q_u = g_u + B^T tilde V_x ; tilde Q_x = g_x + A^T tilde V_x   (:383-384)
-    const real tQu0 = L.h0 + (J.b00 * tv[0] + J.b10 * tv[1] + J.b30 * tv[3]);
-    const real tQu1 = L.h1 + (J.b21 * tv[2] + J.b31 * tv[3]);
-    real tQx[4];
-    tQx[0] = L.g0 + (tv[0] + J.a30 * tv[3]);
-    tQx[1] = L.g1 + (tv[1] + J.a31 * tv[3]);
-    tQx[2] = L.g2 + (J.a02 * tv[0] + J.a12 * tv[1] + tv[2] + J.a32 * tv[3]);
-    tQx[3] = L.g3 + J.g * tv[3];
-    const bool act0 = (L.u0 <= p.umin0 + p.active_tol) || (L.u0 >= p.umax0 - p.active_tol);
-    const bool act1 = (L.u1 <= p.umin1 + p.active_tol) || (L.u1 >= p.umax1 - p.active_tol);
-    const real m00 = Quu[0][0] + reg, m11 = Quu[1][1] + reg;
-    const LU2<real> f = lu2(m00, Quu[0][1], Quu[1][0], m11);
-    real Kk[8], kf[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      real y0, y1;
-      solve_reduced(f, m00, m11, act0, act1, Qux[0][j], Qux[1][j], y0, y1);
-      Kk[j] = -y0;
-      Kk[4 + j] = -y1;
-    }
-    {
-      real y0, y1;
-      solve_reduced(f, m00, m11, act0, act1, tQu0, tQu1, y0, y1);
-      kf[0] = -y0;
-      kf[1] = -y1;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      R.Vx[r] = tQx[r] + (Qxu[r][0] * kf[0] + Qxu[r][1] * kf[1]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) R.Vxx[r][j] = Qxx[r][j] + (Qxu[r][0] * Kk[j] + Qxu[r][1] * Kk[4 + j]);
-    }
-    real* w = W + (size_t)(kLayerRec * k) * nb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) w[(size_t)j * nb] = Kk[j];
-    w[(size_t)8 * nb] = kf[0];
-    w[(size_t)9 * nb] = kf[1];
-    w[(size_t)10 * nb] = J.a02;
-    w[(size_t)11 * nb] = J.a12;
-    w[(size_t)12 * nb] = J.a30;
-    w[(size_t)13 * nb] = J.a31;
-    w[(size_t)14 * nb] = J.a32;
-    w[(size_t)15 * nb] = J.b00;
-    w[(size_t)16 * nb] = J.b10;
-    w[(size_t)17 * nb] = J.b30;
-    w[(size_t)18 * nb] = J.b31;
-    w[(size_t)19 * nb] = real((act0 ? 1 : 0) + (act1 ? 2 : 0));
-  }
-  // forward (:413-425) fused with the accumulation
-  const real* XR = TRACK ? a.Xr + i : nullptr;
-  const real* UR = TRACK ? a.Ur + i : nullptr;
-  real* GXR = TRACK && a.gxr ? a.gxr + i : nullptr;
-  real* GUR = TRACK && a.gur ? a.gur + i : nullptr;
-  auto fload = [&](LFwdIn& F, int k) {
-    const real* w = W + (size_t)(kLayerRec * k) * nb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) F.K[j] = w[(size_t)j * nb];
-    F.kf[0] = w[(size_t)8 * nb];
-    F.kf[1] = w[(size_t)9 * nb];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) F.A[j] = w[(size_t)(10 + j) * nb];
-    F.act = w[(size_t)19 * nb];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) F.x[j] = X[(size_t)(4 * k + j) * nb];
-    F.u[0] = U[(size_t)(2 * k) * nb];
-    F.u[1] = U[(size_t)(2 * k + 1) * nb];
-    if (TRACK) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) F.r[j] = XR[(size_t)(3 * k + j) * nb];
-      F.q[0] = UR[(size_t)(2 * k) * nb];
-      F.q[1] = UR[(size_t)(2 * k + 1) * nb];
-    } else {
-      F.r[0] = c.tg.x;
-      F.r[1] = c.tg.y;
-      F.r[2] = c.tg.z;
-      F.q[0] = F.q[1] = 0.f;
-    }
-  };
-  real d[4] = {0.f, 0.f, 0.f, 0.f};
-  real gQ[3] = {0.f, 0.f, 0.f}, gR[2] = {0.f, 0.f}, gqb = 0.f, gT[3] = {0.f, 0.f, 0.f};
-  const real Qw[3] = {c.Q0, c.Q1, c.Q2}, Rw[2] = {c.R0, c.R1}, Qfw[3] = {c.Qf0, c.Qf1, c.Qf2};
-  const real g = p.gamma, dt = p.dt;
-  bool ok = true;
-  LFwdIn Fn;
-  fload(Fn, 0);
-  for (int k = 0; k < N; ++k) {
-    const LFwdIn F = Fn;
-    if (k + 1 < N) fload(Fn, k + 1);
-    const int act = (int)F.act;
-    const real v0 = (act & 1) ? 0.f : F.kf[0] + (F.K[0] * d[0] + F.K[1] * d[1] + F.K[2] * d[2] + F.K[3] * d[3]);
-    const real v1 = (act & 2) ? 0.f : F.kf[1] + (F.K[4] * d[0] + F.K[5] * d[1] + F.K[6] * d[2] + F.K[7] * d[3]);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      gQ[j] += 2.f * (F.x[j] - F.r[j]) * d[j];
-      const real gr = -(2.f * Qw[j]) * d[j];
-      if (TRACK) {
-        if (GXR) GXR[(size_t)(3 * k + j) * nb] = gr;
-        ok = ok && finite(gr);
-      } else {
-        gT[j] += gr;
-      }
-    }
-    gR[0] += 2.f * (F.u[0] - F.q[0]) * v0;
-    gR[1] += 2.f * (F.u[1] - F.q[1]) * v1;
-    gqb += 2.f * F.x[3] * d[3];
-    if (TRACK) {
-      const real h0 = -(2.f * Rw[0]) * v0, h1 = -(2.f * Rw[1]) * v1;
-      if (GUR) {
-        GUR[(size_t)(2 * k) * nb] = h0;
-        GUR[(size_t)(2 * k + 1) * nb] = h1;
-      }
-      ok = ok && finite(h0) && finite(h1);
-    }
-    // delta x_{k+1} = A delta x_k + B delta u_k
-    const real a02 = F.A[0], a12 = F.A[1], a30 = F.A[2], a31 = F.A[3], a32 = F.A[4], b00 = F.A[5], b10 = F.A[6],
-               b30 = F.A[7], b31 = F.A[8];
-    const real n0 = (d[0] + a02 * d[2]) + b00 * v0;
-    const real n1 = (d[1] + a12 * d[2]) + b10 * v0;
-    const real n2 = d[2] + dt * v1;
-    const real n3 = (a30 * d[0] + a31 * d[1] + a32 * d[2] + g * d[3]) + (b30 * v0 + b31 * v1);
-    d[0] = n0;
-    d[1] = n1;
-    d[2] = n2;
-    d[3] = n3;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) ok = ok && finite(d[j]);
-  real gQf[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const real xn = X[(size_t)(4 * N + j) * nb];
-    const real rn = TRACK ? XR[(size_t)(3 * N + j) * nb] : (j == 0 ? c.tg.x : j == 1 ? c.tg.y : c.tg.z);
-    gQf[j] = 2.f * (xn - rn) * d[j];
-    const real gr = -(2.f * Qfw[j]) * d[j];
-    if (TRACK) {
-      if (GXR) GXR[(size_t)(3 * N + j) * nb] = gr;
-      ok = ok && finite(gr);
-    } else {
-      gT[j] += gr;
-    }
-  }
-  gqb += 2.f * X[(size_t)(4 * N + 3) * nb] * d[3];
-  real* GW = a.gw + i;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    GW[(size_t)j * nb] = gQ[j];
-    GW[(size_t)(5 + j) * nb] = gQf[j];
-    ok = ok && finite(gQ[j]) && finite(gQf[j]);
-  }
-  GW[(size_t)3 * nb] = gR[0];
-  GW[(size_t)4 * nb] = gR[1];
-  GW[(size_t)8 * nb] = gqb;
-  ok = ok && finite(gR[0]) && finite(gR[1]) && finite(gqb);
-  if (!TRACK) {
-    if (a.gt) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) a.gt[(size_t)j * nb + i] = gT[j];
-    }
-    ok = ok && finite(gT[0]) && finite(gT[1]) && finite(gT[2]);
-  }
-  if (!ok) a.status[i] |= DTMPC_ST_NONFINITE;
+  constexpr bool GEOM = false;
+  real* const gx0 = nullptr;
+  real* const gob = nullptr;
+#include "dtmpc_fast_layer_body.hpp"
+}
+// ... and with the rows w.r.t. the start state and the obstacle circles (dtmpc_solve_backward_geom)
+template <int M, bool TRACK>
+__global__ void __launch_bounds__(kBlock) solve_backward_geom_kernel(LKG kg) {
+  constexpr bool GEOM = true;
+  const LK& kk = kg.k;
+  real* const gx0 = kg.gx0;
+  real* const gob = kg.gob;
+#include "dtmpc_fast_layer_body.hpp"
 }
 
 }  // namespace fk
@@ -296,38 +141,98 @@ static const char* layer_unsupported(int dtype, const dtmpc_spec* sp, const dtmp
   return nullptr;
 }
 
-static size_t layer_workspace_bytes(int32_t N, int64_t B) {
-  return (size_t)N * fk::kLayerRec * sizeof(real) * (size_t)B;
+static size_t layer_workspace_bytes(int32_t N, int64_t B, bool geom = false) {
+  return (size_t)N * (geom ? fk::kGeomRec : fk::kLayerRec) * sizeof(real) * (size_t)B;
 }
 
+// geom: solve_backward_geom_kernel with the two further outputs (either may be NULL), else solve_backward_kernel
 static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int64_t B, const fk::LArgs& a,
-                                 hipStream_t st) {
-  fk::LK kk;
-  std::memset(&kk, 0, sizeof(kk));
+                                 hipStream_t st, bool geom = false, real* gx0 = nullptr, real* gob = nullptr) {
+  fk::LKG kg;
+  std::memset(&kg, 0, sizeof(kg));
+  fk::LK& kk = kg.k;
   fast_p(sp, kk.p);
   const DCost<real> c = make_cost<real>(*cp);
   const bool track = cp->kind == DTMPC_COST_TRACK;
   kk.c = fk::FCost{c.Q0, c.Q1, c.Q2, c.R0, c.R1, c.Qf0, c.Qf1, c.Qf2, c.qb,
                    track ? fk::f4{0.f, 0.f, 0.f, 0.f} : fk::f4{c.t0, c.t1, c.t2, 0.f}};
   kk.a = a;
+  kg.gx0 = gx0;
+  kg.gob = gob;
   const int bs = tube_block(B, 1);
   const dim3 grid((unsigned)((B + bs - 1) / bs));
-#define LY_LAUNCH(m, t) hipLaunchKernelGGL((fk::solve_backward_kernel<m, t>), grid, dim3(bs), 0, st, kk)
 #define LY_CASE(m) \
   case m:          \
     if (track) LY_LAUNCH(m, true); else LY_LAUNCH(m, false); \
     break;
-  switch (sp->n_obstacles) {
 #ifdef DTMPC_FAST_M_ONLY
-    LY_CASE(DTMPC_FAST_M_ONLY)
+#define LY_CASES LY_CASE(DTMPC_FAST_M_ONLY)
 #else
-    LY_CASE(1) LY_CASE(2) LY_CASE(3) LY_CASE(4) LY_CASE(5) LY_CASE(6) LY_CASE(7) LY_CASE(8)
+#define LY_CASES LY_CASE(1) LY_CASE(2) LY_CASE(3) LY_CASE(4) LY_CASE(5) LY_CASE(6) LY_CASE(7) LY_CASE(8)
 #endif
-    default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
-  }
-#undef LY_CASE
+  if (!geom) {
+#define LY_LAUNCH(m, t) hipLaunchKernelGGL((fk::solve_backward_kernel<m, t>), grid, dim3(bs), 0, st, kk)
+    switch (sp->n_obstacles) {
+      LY_CASES
+      default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
+    }
 #undef LY_LAUNCH
-  return check_launch("solve_backward_kernel");
+  } else {
+#define LY_LAUNCH(m, t) hipLaunchKernelGGL((fk::solve_backward_geom_kernel<m, t>), grid, dim3(bs), 0, st, kg)
+    switch (sp->n_obstacles) {
+      LY_CASES
+      default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
+    }
+#undef LY_LAUNCH
+  }
+#undef LY_CASES
+#undef LY_CASE
+  return check_launch(geom ? "solve_backward_geom_kernel" : "solve_backward_kernel");
+}
+
+// dtmpc_solve_backward and dtmpc_solve_backward_geom: the argument rules of include/dtmpc.h, then the launch
+static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
+                                const void* X, const void* U, const void* Xref, const void* Uref, const void* scenes,
+                                const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
+                                void* g_x0, void* g_obs, void* work, size_t work_bytes, int32_t* status,
+                                void* stream) {
+  if (!spec || !cost) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL spec or cost");
+  if (B < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: batch must be >= 1");
+  if (spec->horizon < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: horizon must be >= 1");
+  if (int r = check_spec(spec, B)) return r;
+  if (cost->kind != DTMPC_COST_TARGET && cost->kind != DTMPC_COST_TRACK)
+    return set_err(DTMPC_ERR_BAD_ARG, "solve backward: bad cost kind");
+  if (const char* why = layer_unsupported(dtype, spec, cost)) return set_err(DTMPC_ERR_BAD_ARG, why);
+  if (!X || !U || !gX || !gU || !g_w || !status)
+    return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL X, U, gX, gU, g_w or status");
+  if (geom && !g_x0 && !g_obs)
+    return set_err(DTMPC_ERR_BAD_ARG, "solve backward geom: g_x0 and g_obs both NULL (that is dtmpc_solve_backward)");
+  if (cost->kind == DTMPC_COST_TRACK) {
+    if (!Xref || !Uref) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: the tracking cost needs Xref and Uref");
+    if (g_target) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: g_target goes with the target cost");
+  } else if (Xref || Uref || g_xref || g_uref) {
+    return set_err(DTMPC_ERR_BAD_ARG, "solve backward: Xref, Uref, g_xref and g_uref go with the tracking cost");
+  }
+  if (!work || work_bytes < layer_workspace_bytes(spec->horizon, B, geom))
+    return set_err(DTMPC_ERR_BAD_ARG, geom ? "solve backward geom: work_bytes < "
+                                             "dtmpc_solve_backward_geom_workspace_bytes(...)"
+                                           : "solve backward: work_bytes < dtmpc_solve_backward_workspace_bytes(...)");
+  fk::LArgs a;
+  a.B = (int)B;
+  a.X = (const real*)X;
+  a.U = (const real*)U;
+  a.Xr = (const real*)Xref;
+  a.Ur = (const real*)Uref;
+  a.sc = (const real*)scenes;
+  a.gX = (const real*)gX;
+  a.gU = (const real*)gU;
+  a.gw = (real*)g_w;
+  a.gt = (real*)g_target;
+  a.gxr = (real*)g_xref;
+  a.gur = (real*)g_uref;
+  a.work = (real*)work;
+  a.status = status;
+  return launch_solve_backward(spec, cost, B, a, (hipStream_t)stream, geom, (real*)g_x0, (real*)g_obs);
 }
 
 }  // namespace dtmpc
@@ -347,40 +252,21 @@ int dtmpc_solve_backward(int dtype, const dtmpc_spec* spec, const dtmpc_cost* co
                          const void* U, const void* Xref, const void* Uref, const void* scenes, const void* gX,
                          const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref, void* work,
                          size_t work_bytes, int32_t* status, void* stream) {
-  using namespace dtmpc;
-  if (!spec || !cost) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL spec or cost");
-  if (B < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: batch must be >= 1");
-  if (spec->horizon < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: horizon must be >= 1");
-  if (int r = check_spec(spec, B)) return r;
-  if (cost->kind != DTMPC_COST_TARGET && cost->kind != DTMPC_COST_TRACK)
-    return set_err(DTMPC_ERR_BAD_ARG, "solve backward: bad cost kind");
-  if (const char* why = layer_unsupported(dtype, spec, cost)) return set_err(DTMPC_ERR_BAD_ARG, why);
-  if (!X || !U || !gX || !gU || !g_w || !status)
-    return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL X, U, gX, gU, g_w or status");
-  if (cost->kind == DTMPC_COST_TRACK) {
-    if (!Xref || !Uref) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: the tracking cost needs Xref and Uref");
-    if (g_target) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: g_target goes with the target cost");
-  } else if (Xref || Uref || g_xref || g_uref) {
-    return set_err(DTMPC_ERR_BAD_ARG, "solve backward: Xref, Uref, g_xref and g_uref go with the tracking cost");
-  }
-  if (!work || work_bytes < layer_workspace_bytes(spec->horizon, B))
-    return set_err(DTMPC_ERR_BAD_ARG, "solve backward: work_bytes < dtmpc_solve_backward_workspace_bytes(...)");
-  fk::LArgs a;
-  a.B = (int)B;
-  a.X = (const real*)X;
-  a.U = (const real*)U;
-  a.Xr = (const real*)Xref;
-  a.Ur = (const real*)Uref;
-  a.sc = (const real*)scenes;
-  a.gX = (const real*)gX;
-  a.gU = (const real*)gU;
-  a.gw = (real*)g_w;
-  a.gt = (real*)g_target;
-  a.gxr = (real*)g_xref;
-  a.gur = (real*)g_uref;
-  a.work = (real*)work;
-  a.status = status;
-  return launch_solve_backward(spec, cost, B, a, (hipStream_t)stream);
+  return dtmpc::solve_backward_entry(false, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, nullptr, nullptr, work, work_bytes, status, stream);
+}
+
+size_t dtmpc_solve_backward_geom_workspace_bytes(int dtype, int32_t horizon, int64_t B) {
+  if (dtype != DTMPC_F32 || horizon < 1 || B < 1) return 0;
+  return dtmpc::layer_workspace_bytes(horizon, B, true);
+}
+
+int dtmpc_solve_backward_geom(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B, const void* X,
+                              const void* U, const void* Xref, const void* Uref, const void* scenes, const void* gX,
+                              const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref, void* g_x0,
+                              void* g_obs, void* work, size_t work_bytes, int32_t* status, void* stream) {
+  return dtmpc::solve_backward_entry(true, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, g_x0, g_obs, work, work_bytes, status, stream);
 }
 
 }  // extern "C"

@@ -8,11 +8,19 @@ upper gradients, then ift_gradient's accumulation (core/ift.py:35-92) restricted
 and the references.  It is the quantity the paper's Algorithm 2 descends along.  It is the gradient of the solver's
 output only where the solve has converged: on a tape that is not a stationary point of the lower problem (an
 iteration cap, a failed line search) it is still well defined, but it is the sensitivity of the KKT system
-linearised there, not of the iterate.  Gradients w.r.t. x0, the warm start, the obstacle geometry and the DBaS
-parameters (alpha, gamma, tightening) are not provided; the last remain ``ift_gradient``'s.
+linearised there, not of the iterate.  On request (``want_x0`` / ``want_obstacles``; ``wrt=`` of the layer) the rows
+w.r.t. the start state and the obstacle circles come with them: the two terms of ift_gradient that involve
+delta_lambda,
+    g_x0 = dlam_0 = tilde V_x[0]
+    c_m = B'(h(x_m)) ([m >= 1] lam_m - gamma [m <= N-1] lam_{m+1}),  lam_k = dlam_k[3]          m = 0 .. N
+    g_cx_j = sum_m c_m w_j(x_m) (-2 (px_m - cx_j)),  g_cy_j alike,  g_r_j = 2 r_j sum_m c_m w_j(x_m) (-1)
+with w_j = softmax_j(-beta h_j) (only the barrier row of f_hat sees the obstacles).  b_0's own dependence on the
+position and the scene is the caller's to express (``dbas_init_b0`` is differentiable).  Gradients w.r.t. the warm
+start and the DBaS parameters (alpha, gamma, tightening) are not provided; the last remain ``ift_gradient``'s.
 
 Where ``dtmpc_solve_backward_supported`` says yes (f32, smooth-min, 1..8 obstacles, relaxed inverse barrier) the
-rows come from ONE launch of the fused kernel (csrc/dtmpc_fast_layer.hip), which writes no sensitivity tape;
+rows come from ONE launch of the fused kernel (csrc/dtmpc_fast_layer.hip; dtmpc_solve_backward_geom when x0 or
+obstacle rows are wanted), which writes no sensitivity tape;
 elsewhere (f64, min / single aggregation, log barrier) from ``dtmpc_ddp_sensitivity_upper`` and a few tensor
 operations."""
 from __future__ import annotations
@@ -20,12 +28,13 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 from torch import Tensor
 
 from .. import _abi, _lib
+from .barrier import barrier_and_derivative
 from .ddp import (ILQRResult, _ddp_sensitivity_upper, _dtype_code, _ptr, _require_device, from_soa, ilqr_solve,
                   raise_for_status, to_soa)
 from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, pack_scenes
@@ -42,6 +51,8 @@ class SolveGradient:
     X_ref: Optional[Tensor]    # [B, N+1, 3] (tracking cost)
     U_ref: Optional[Tensor]    # [B, N, 2]
     status: Tensor             # [B] int32, DTMPC_ST_NONFINITE where a row is not finite
+    x0: Optional[Tensor] = None         # [B, 4] (want_x0)
+    obstacles: Optional[Tensor] = None  # [B, M, 3]: (cx, cy, r) of each circle (want_obstacles)
 
 
 def _nonfinite_status(*rows: Optional[Tensor]) -> Tensor:
@@ -54,9 +65,29 @@ def _nonfinite_status(*rows: Optional[Tensor]) -> Tensor:
     return bad.to(torch.int32) * _abi.ST_NONFINITE
 
 
+def _obstacle_rows(problem: DubinsDBaSProblem, X: Tensor, dlam: Tensor) -> Tensor:
+    """The obstacle rows [B, M, 3] (cx, cy, r) from a sensitivity's delta_lambda [B, N+1, 4] as tensor operations
+    (the module docstring's formulas; smooth-min and the relaxed inverse barrier, the problem's shared circles)."""
+    kw = dict(dtype=X.dtype, device=X.device)
+    tab = torch.tensor([[o.center[0], o.center[1], o.radius] for o in problem.obstacles], **kw)
+    dx = X[..., 0:1] - tab[:, 0]  # [B, N+1, M]
+    dy = X[..., 1:2] - tab[:, 1]
+    z = -float(problem.obs_beta) * (dx * dx + dy * dy - tab[:, 2] * tab[:, 2])
+    w = torch.softmax(z, -1)
+    h = -torch.logsumexp(z, -1) / float(problem.obs_beta)
+    D = barrier_and_derivative(h, kind=_abi.BARRIER_INVERSE, alpha=float(problem.dbas_alpha),
+                               eps=float(problem.dbas_eps), want_B=False, want_dB=True)[1]
+    lam = dlam[..., 3]
+    zero = torch.zeros_like(lam[:, :1])
+    c = D * (torch.cat([zero, lam[:, 1:]], 1) - float(problem.dbas_gamma) * torch.cat([lam[:, 1:], zero], 1))
+    cw = c[..., None] * w
+    return torch.stack([(cw * (-2.0 * dx)).sum(1), (cw * (-2.0 * dy)).sum(1), -cw.sum(1) * (2.0 * tab[:, 2])], 2)
+
+
 def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor, V: Tensor, grad_X: Tensor,
                    grad_V: Tensor, X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
-                   scenes: Optional[Tensor] = None, check: bool = True) -> SolveGradient:
+                   scenes: Optional[Tensor] = None, check: bool = True, want_x0: bool = False,
+                   want_obstacles: bool = False) -> SolveGradient:
     """The gradient of an upper loss w.r.t. the plain cost weights and the references, per trajectory, from the
     loss's gradients ``grad_X`` [B, N+1, 4] / ``grad_V`` [B, N, 2] w.r.t. the tape (X [B, N+1, 4], V [B, N, 2]).
 
@@ -67,7 +98,12 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
     cost.kind 'track' needs X_ref [B, N+1, >=3] and U_ref [B, N, 2] and returns their gradient rows; 'target'
     returns the target's.  scenes ([3M + 3, B], pack_scenes): trajectory i linearises with its own obstacles and a
     target cost uses its own target (fused f32 kernel only).  check: raise FloatingPointError on a non-finite row
-    (else see ``status``)."""
+    (else see ``status``).
+
+    want_x0 / want_obstacles: also the rows w.r.t. the start state (``x0`` [B, 4]: x, y, heading, b) and the circles
+    (``obstacles`` [B, M, 3]: cx, cy, r -- trajectory i's own circles with scenes, whose radii are the roots of the
+    scene's squared radii).  x0 rows come on every path; obstacle rows need smooth-min aggregation and the relaxed
+    inverse barrier (the fused kernel, or on f64 the composition without scenes)."""
     if cost.wrap_angle:
         raise ValueError("solve_backward: a cost with wrap_angle is not supported (the reference's sensitivity "
                          "closures carry no wrapped heading error)")
@@ -86,9 +122,12 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
     spec, cc = problem.to_c(), cost.to_c()
     dt, dev = X.dtype, X.device
     kw = dict(dtype=dt, device=dev)
-    if lib.dtmpc_solve_backward_supported(_dtype_code(X), C.byref(spec), C.byref(cc)):
+    geom = want_x0 or want_obstacles
+    M = len(problem.obstacles)
+    fused = bool(lib.dtmpc_solve_backward_supported(_dtype_code(X), C.byref(spec), C.byref(cc)))
+    if fused:
         if scenes is not None:
-            check_scenes(scenes, len(problem.obstacles), B, dt, dev)
+            check_scenes(scenes, M, B, dt, dev)
         Xs, Us, gx, gu = to_soa(X), to_soa(V.to(dt)), to_soa(grad_X.to(dt)), to_soa(grad_V.to(dt))
         Xr = to_soa(X_ref[..., :3].to(dt)) if track else None
         Ur = to_soa(U_ref.to(dt)) if track else None
@@ -96,23 +135,40 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         gt = None if track else torch.empty(3, B, **kw)
         gxr = torch.empty(N + 1, 3, B, **kw) if track else None
         gur = torch.empty(N, 2, B, **kw) if track else None
-        wb = int(lib.dtmpc_solve_backward_workspace_bytes(_dtype_code(X), N, B))
+        gx0 = torch.empty(4, B, **kw) if want_x0 else None
+        gob = torch.empty(3, M, B, **kw) if want_obstacles else None
+        nbytes = lib.dtmpc_solve_backward_geom_workspace_bytes if geom else lib.dtmpc_solve_backward_workspace_bytes
+        wb = int(nbytes(_dtype_code(X), N, B))
         work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
-        _lib.check(lib.dtmpc_solve_backward(_dtype_code(X), C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(),
-                                            _ptr(Xr), _ptr(Ur), _ptr(scenes), gx.data_ptr(), gu.data_ptr(),
-                                            gw.data_ptr(), _ptr(gt), _ptr(gxr), _ptr(gur), work.data_ptr(), wb,
-                                            status.data_ptr(), _lib.stream_of(X)), "dtmpc_solve_backward")
+        head = (_dtype_code(X), C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), _ptr(Xr), _ptr(Ur),
+                _ptr(scenes), gx.data_ptr(), gu.data_ptr(), gw.data_ptr(), _ptr(gt), _ptr(gxr), _ptr(gur))
+        tail = (work.data_ptr(), wb, status.data_ptr(), _lib.stream_of(X))
+        if geom:  # the GEOM variant of the kernel: the same rows, and those w.r.t. x0 / (cx, cy, r^2)
+            _lib.check(lib.dtmpc_solve_backward_geom(*head, _ptr(gx0), _ptr(gob), *tail), "dtmpc_solve_backward_geom")
+        else:
+            _lib.check(lib.dtmpc_solve_backward(*head, *tail), "dtmpc_solve_backward")
+        rows = None
+        if want_obstacles:  # d r^2 / d r = 2 r; a scene holds r^2 only
+            if scenes is not None:
+                r = torch.sqrt(scenes[2 * M:3 * M])  # [M, B]
+            else:
+                r = torch.tensor([o.radius for o in problem.obstacles], **kw)[:, None]
+            rows = torch.stack([gob[0], gob[1], gob[2] * (2.0 * r)], 2).permute(1, 0, 2).contiguous()
         out = SolveGradient(weights=gw.t().contiguous(), target=None if track else gt.t().contiguous(),
                             X_ref=from_soa(gxr) if track else None, U_ref=from_soa(gur) if track else None,
-                            status=status)
+                            status=status, x0=gx0.t().contiguous() if want_x0 else None, obstacles=rows)
     else:
         if scenes is not None:
             raise ValueError("solve_backward: per-trajectory scenes need the fused kernel "
                              "(dtmpc_solve_backward_supported: f32, smooth-min, 1..8 obstacles, inverse barrier)")
         if spec.h_offset != 0.0:
             raise ValueError("solve_backward: a tightened h (h_offset) is not supported")
-        s = _ddp_sensitivity_upper(problem, cost, X, V, grad_X, grad_V, False, False)
+        if want_obstacles and (problem.obs_aggregation != "smoothmin" or problem.barrier_type != "inverse" or M < 1):
+            raise ValueError("solve_backward: obstacle rows need smooth-min aggregation and the relaxed inverse "
+                             "barrier (min / single aggregation have no softmax weights; the log barrier's rows "
+                             "are not provided)")
+        s = _ddp_sensitivity_upper(problem, cost, X, V, grad_X, grad_V, geom, False)
         dX, dV = s.delta_X, s.delta_V
         Q = torch.tensor(cost.Q, **kw)
         R = torch.tensor(cost.R, **kw)
@@ -131,23 +187,28 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         gur = -2.0 * R * dV
         gw = torch.cat([gQ, gR, gQf, gqb], 1)
         gt = None if track else gxr.sum(1)
-        status = _nonfinite_status(gw, gt, gxr if track else None, gur if track else None, dX[:, N])
+        gx0 = s.delta_lambda[:, 0].contiguous() if want_x0 else None
+        gob = _obstacle_rows(problem, X, s.delta_lambda) if want_obstacles else None
+        status = _nonfinite_status(gw, gt, gxr if track else None, gur if track else None, dX[:, N], gx0, gob)
         out = SolveGradient(weights=gw, target=gt, X_ref=gxr if track else None, U_ref=gur if track else None,
-                            status=status)
+                            status=status, x0=gx0, obstacles=gob)
     if check:
         raise_for_status(out.status, "solve_backward")
     return out
 
 
 class _Solve(torch.autograd.Function):
-    """X*, V* of a finished solve as functions of the weight / reference tensors: forward hands the tape through,
+    """X*, V* of a finished solve as functions of the weight / reference tensors (and, named in ``wrt``, of the
+    start state and the obstacle circles: x0 / obstacles are None otherwise): forward hands the tape through,
     backward is solve_backward at that tape."""
 
     @staticmethod
-    def forward(ctx, X, V, problem, cost, scenes, per_traj_target, nref, Q, R, Qf, qb, target, X_ref, U_ref):
+    def forward(ctx, X, V, problem, cost, scenes, per_traj_target, nref, Q, R, Qf, qb, target, X_ref, U_ref,
+                x0=None, obstacles=None):
         ctx.problem, ctx.cost, ctx.scenes = problem, cost, scenes
         ctx.per_traj_target, ctx.nref = per_traj_target, nref
-        ctx.shapes = tuple(None if t is None else (t.shape, t.dtype) for t in (Q, R, Qf, qb, target, X_ref, U_ref))
+        ctx.shapes = tuple(None if t is None else (t.shape, t.dtype)
+                           for t in (Q, R, Qf, qb, target, X_ref, U_ref, x0, obstacles))
         ctx.save_for_backward(X, V, *(t for t in (X_ref, U_ref) if t is not None))
         ctx.flagged = None
         return X.clone(), V.clone()
@@ -158,9 +219,12 @@ class _Solve(torch.autograd.Function):
         Xr, Ur = (refs + [None, None])[:2]
         gX = torch.zeros_like(X) if gX is None else gX
         gV = torch.zeros_like(V) if gV is None else gV
+        sh = ctx.shapes
+        need = ctx.needs_input_grad[7:]
         g = solve_backward(problem=ctx.problem, cost=ctx.cost, X=X, V=V, grad_X=gX.contiguous(),
                            grad_V=gV.contiguous(), X_ref=None if Xr is None else Xr.detach(),
-                           U_ref=None if Ur is None else Ur.detach(), scenes=ctx.scenes, check=False)
+                           U_ref=None if Ur is None else Ur.detach(), scenes=ctx.scenes, check=False,
+                           want_x0=sh[7] is not None and need[7], want_obstacles=sh[8] is not None and need[8])
         keep = (g.status == 0)
         ctx.flagged = g.status  # [B] int32: the trajectories left out of this backward
 
@@ -169,9 +233,7 @@ class _Solve(torch.autograd.Function):
 
         w = rows(g.weights)
         ws = w.sum(0)
-        out = [None] * 7
-        need = ctx.needs_input_grad[7:]
-        sh = ctx.shapes
+        out = [None] * 9
         for j, sl in enumerate((slice(0, 3), slice(3, 5), slice(5, 8), slice(8, 9))):
             if sh[j] is not None and need[j]:
                 out[j] = ws[sl].reshape(sh[j][0]).to(sh[j][1])
@@ -185,6 +247,11 @@ class _Solve(torch.autograd.Function):
             out[5] = gx.to(sh[5][1])
         if sh[6] is not None and need[6] and g.U_ref is not None:
             out[6] = rows(g.U_ref).to(sh[6][1])
+        if g.x0 is not None:
+            out[7] = rows(g.x0).to(sh[7][1])
+        if g.obstacles is not None:  # [M, 3]: the shared circles get the sum over the batch
+            o = rows(g.obstacles)
+            out[8] = (o.sum(0) if len(sh[8][0]) == 2 else o).to(sh[8][1])
         return (None,) * 7 + tuple(out)
 
 
@@ -202,7 +269,8 @@ class DiffILQRResult(ILQRResult):
 def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q: Tensor, R: Tensor, Qf: Tensor,
                     qb: Tensor, x0: Tensor, V_init: Tensor, target: Optional[Tensor] = None,
                     X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
-                    obstacles: Optional[Tensor] = None, lanes: int = 0, check: bool = True) -> ILQRResult:
+                    obstacles: Optional[Tensor] = None, lanes: int = 0, check: bool = True,
+                    wrt: Sequence[str] = ()) -> ILQRResult:
     """``ilqr_solve`` whose X* / V* are differentiable w.r.t. Q [3], R [2], Qf [3], qb [], the target ([3] shared
     or [B, 3] per trajectory; kind 'target') and X_ref [B, N+1, >=3] / U_ref [B, N, 2] (kind 'track').
 
@@ -219,15 +287,29 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
     contributes zero rows; ``result.backward_status()`` holds the flags of the last backward.  The same tensor
     passed twice (say as Q and Qf) accumulates both gradients, as autograd does.
 
-    Refused: gradients w.r.t. x0 and V_init (the reference detaches xi, and the warm start is not an argument of
-    the optimum), w.r.t. obstacles, a wrapped heading error, and DBaS parameters as tensors (their gradients remain
+    wrt (opt-in): ``"x0"`` -- x0 [B, 4] may require grad and receives its rows (g_x0 = dlam_0; b_0's dependence on
+    the position is the caller's: ``dbas_init_b0`` is differentiable), so solves chain: plan, step the plant, plan
+    again, one ``backward()`` through both.  ``"obstacles"`` -- ``obstacles`` ([B, M, 3] per trajectory, or [M, 3]
+    shared, expanded through ``pack_scenes``) may require grad and receives its rows (the [M, 3] form their sum over
+    the batch), see the module docstring.
+
+    Refused: without ``wrt`` gradients w.r.t. x0 and obstacles; always w.r.t. V_init (the warm start is not an
+    argument of the optimum), a wrapped heading error, and DBaS parameters as tensors (their gradients remain
     ``ift_gradient``'s).  check: the forward raises as ``ilqr_solve`` does."""
     if kind not in ("target", "track"):
         raise ValueError(f"unknown cost kind {kind!r}")
-    if x0.requires_grad or V_init.requires_grad:
+    if isinstance(wrt, str) or any(w not in ("x0", "obstacles") for w in wrt):
+        raise ValueError(f"diff_ilqr_solve: wrt is a sequence of 'x0' and / or 'obstacles', got {wrt!r}")
+    wrt_x0, wrt_obs = "x0" in wrt, "obstacles" in wrt
+    if wrt_obs and not isinstance(obstacles, Tensor):
+        raise ValueError("diff_ilqr_solve: wrt 'obstacles' needs obstacles as a tensor ([B, M, 3] or [M, 3])")
+    if V_init.requires_grad and wrt_x0:
+        raise ValueError("diff_ilqr_solve: no gradient w.r.t. V_init -- the warm start is not an argument of the "
+                         "optimum; detach it")
+    if (x0.requires_grad and not wrt_x0) or V_init.requires_grad:
         raise ValueError("diff_ilqr_solve: no gradient w.r.t. x0 or V_init -- the reference's IFT detaches the "
                          "initial state (xi), and the warm start is not an argument of the optimum; detach them")
-    if obstacles is not None and isinstance(obstacles, Tensor) and obstacles.requires_grad:
+    if obstacles is not None and isinstance(obstacles, Tensor) and obstacles.requires_grad and not wrt_obs:
         raise ValueError("diff_ilqr_solve: no gradient w.r.t. the obstacle geometry; detach obstacles")
     for name in ("dbas_alpha", "dbas_gamma", "dbas_eps", "obs_beta"):
         if isinstance(getattr(problem, name), Tensor):
@@ -258,16 +340,19 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
     scenes = None
     if per_traj or obstacles is not None:
         obs = obstacles
+        if isinstance(obs, Tensor) and obs.dim() == 2:  # shared circles: every trajectory's scene
+            obs = obs.detach().expand(B, *obs.shape)
         if obs is None:
             obs = torch.tensor([[o.center[0], o.center[1], o.radius] for o in problem.obstacles],
                                dtype=torch.float64).expand(B, -1, 3)
         tg = target.detach() if per_traj else (torch.tensor(cost.target, dtype=torch.float64).expand(B, 3))
         scenes = pack_scenes(problem, obs, tg, dtype=x0.dtype, device=x0.device)
-    res = ilqr_solve(problem=problem, cost=cost, cfg=cfg, x0=x0, V_init=V_init,
+    res = ilqr_solve(problem=problem, cost=cost, cfg=cfg, x0=x0.detach(), V_init=V_init,
                      X_ref=None if X_ref is None else X_ref.detach(), U_ref=None if U_ref is None else U_ref.detach(),
                      check=check, debug_name="diff_ilqr_solve", lanes=lanes, scenes=scenes)
     nref = 0 if X_ref is None else X_ref.shape[-1]
-    Xd, Vd = _Solve.apply(res.X, res.V, problem, cost, scenes, per_traj, nref, Q, R, Qf, qb, target, X_ref, U_ref)
+    Xd, Vd = _Solve.apply(res.X, res.V, problem, cost, scenes, per_traj, nref, Q, R, Qf, qb, target, X_ref, U_ref,
+                          x0 if wrt_x0 else None, obstacles if wrt_obs else None)
     fields = {f.name: getattr(res, f.name) for f in dataclasses.fields(ILQRResult)}
     fields.update(X=Xd, V=Vd)
     return DiffILQRResult(**fields, _node=Xd.grad_fn)

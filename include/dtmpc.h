@@ -474,6 +474,32 @@ int dtmpc_solve_backward(int dtype, const dtmpc_spec* spec, const dtmpc_cost* co
                          const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
                          void* work, size_t work_bytes, int32_t* status, void* stream);
 
+/* ... and the rows w.r.t. the start state and the obstacle circles: the two terms of ift_gradient that involve
+ * delta_lambda (dlam_k = tilde V_x[k] + V_xx[k] dx_k, lam_k its barrier-state component), from the same launch --
+ *   g_x0 [4][B] = dlam_0 = tilde V_x[0] (rows x, y, heading, b; b_0's own dependence on the position and the scene
+ *   is the caller's to add);
+ *   g_obs [3M][B], rows cx[0..M), cy[0..M), r2[0..M) in scene order (r2 the SQUARED radius of the scene table:
+ *   d / d r = 2 r d / d r2): with c_m = B'(h(x_m)) ([m >= 1] lam_m - gamma [m <= N-1] lam_{m+1}), m = 0..N, and
+ *   w_j = softmax_j(-beta h_j) at tape row m,
+ *     g_cx[j] = sum_m c_m w_j (-2 (px_m - cx_j)),  g_cy[j] = sum_m c_m w_j (-2 (py_m - cy_j)),  g_r2[j] = -sum_m c_m w_j
+ *   (only the barrier row of f_hat depends on the obstacles).
+ * The kernel is dtmpc_solve_backward's with the barrier row of V_xx and of tilde V_x kept per step (25 values, 100 B
+ * per step and trajectory) and the weights evaluated again in the forward sweep; g_w, g_target, g_xref, g_uref are
+ * the same quantities as dtmpc_solve_backward's and agree with them to rounding (the last few bits differ: another
+ * kernel).  Added beside ABI 8; supported where dtmpc_solve_backward_supported says so. */
+
+/* Scratch bytes of dtmpc_solve_backward_geom: horizon x 100 B per trajectory in f32 (0 as above). */
+size_t dtmpc_solve_backward_geom_workspace_bytes(int dtype, int32_t horizon, int64_t B);
+
+/* dtmpc_solve_backward's arguments and rules, plus g_x0 [4][B] and g_obs [3M][B]: either may be NULL, both NULL is
+ * DTMPC_ERR_BAD_ARG (that call is dtmpc_solve_backward), and work_bytes is held to
+ * dtmpc_solve_backward_geom_workspace_bytes.  With scenes, trajectory i's rows are w.r.t. its own circles.  The status
+ * word also covers the new rows. */
+int dtmpc_solve_backward_geom(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
+                              const void* X, const void* U, const void* Xref, const void* Uref, const void* scenes,
+                              const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
+                              void* g_x0, void* g_obs, void* work, size_t work_bytes, int32_t* status, void* stream);
+
 
 /* ---- general (softplus / tanh parameterised) IFT path ------------------------------------ */
 /*

@@ -25,13 +25,23 @@ def unit(obj):
                               "--no-leading-addr", co], check=True, capture_output=True, text=True).stdout
         notes = subprocess.run([f"{B.LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True,
                                text=True).stdout
-    res, cur = {}, None
+    # one entry of amdhsa.kernels per kernel, its keys in alphabetical order (.args ... .name ... .wavefront_size): an
+    # entry starts at a "- ." line of the list's own indentation (the entries of .args are indented deeper)
+    res, cur, ind = {}, None, None
     for line in notes.splitlines():
+        if line.strip() == "amdhsa.kernels:":
+            cur, ind = None, None
+            continue
+        e = re.match(r"(\s*)- \.", line)
+        if e and (ind is None or len(e.group(1)) <= ind):
+            ind, cur = len(e.group(1)), {}
+            line = line.replace("- ", "  ", 1)
         m = NOTE.match(line)
-        if m and m.group(1) == "name":
-            cur = res.setdefault(m.group(2), {})
-        elif m and cur is not None:
-            cur[m.group(1)] = m.group(2)
+        if m and cur is not None:
+            if m.group(1) == "name":
+                res[m.group(2)] = cur
+            else:
+                cur[m.group(1)] = m.group(2)
     code, name = {}, None
     for line in dis.splitlines():
         m = re.match(r"^<?([_A-Za-z0-9.$]+)>?:\s*$", line)
@@ -40,7 +50,10 @@ def unit(obj):
             continue
         if name:
             # without the trailing "// address: encoding" comment: kernels behind a new one move in the code object
-            code.setdefault(name, []).append(line.split("//")[0].strip())
+            # (and without the "..." / blank lines objdump prints for the padding in front of the next function)
+            t = line.split("//")[0].strip()
+            if t and t != "...":
+                code.setdefault(name, []).append(t)
     return os.path.basename(obj).split(".")[0], {k: ("\n".join(v), res[k]) for k, v in code.items()}
 
 

@@ -9,7 +9,10 @@ and the upper gradients are seeded normals.  Both backward variants run on SoA b
 in the timed region); each figure is the median over `reps` calls between device events after a warm-up of 3, the
 spread max - min of the per-round medians.  `layer_forward` / `layer_backward` time diff_ilqr_solve(...) and
 loss.backward() as a user calls them (layout copies, the weights' device-to-host read and autograd included).  The
-bytes the fused kernel moves by construction are printed beside the times.  One JSON line."""
+bytes the fused kernel moves by construction are printed beside the times.  `fused_geom` / `composition_geom`: the
+same pair for dtmpc_solve_backward_geom (the rows w.r.t. x0 and the obstacle circles as well) -- its composition
+also writes delta_lambda and forms the obstacle rows as tensor operations -- timed in the same alternated rounds, so
+`fused` beside it shows whether the old entry moved.  One JSON line."""
 import argparse
 import ctypes as C
 import json
@@ -23,6 +26,7 @@ import torch  # noqa: E402
 
 from diff_tube_mpc_strict_pt import _abi, _lib  # noqa: E402
 from diff_tube_mpc_strict_pt.core import dbas_init, diff_ilqr_solve, ilqr_solve  # noqa: E402
+from diff_tube_mpc_strict_pt.core.barrier import barrier_and_derivative  # noqa: E402
 from diff_tube_mpc_strict_pt.core.ddp import to_soa  # noqa: E402
 from diff_tube_mpc_strict_pt.core.problem import paper_config, paper_setup_from_config  # noqa: E402
 
@@ -86,6 +90,9 @@ def main():
                                                    gx.data_ptr(), gu.data_ptr(), dX.data_ptr(), dU.data_ptr(), None,
                                                    work2.data_ptr(), status.data_ptr(), stream),
                    "dtmpc_ddp_sensitivity_upper")
+        composition_rows()
+
+    def composition_rows():
         ex = Xs[:, :3] - tg
         gQ = (2 * ex[:N] * dX[:N, :3]).sum(0)
         gR = (2 * Us * dU).sum(0)
@@ -93,6 +100,41 @@ def main():
         gqb = (2 * Xs[:, 3] * dX[:, 3]).sum(0, keepdim=True)
         comp["gw"] = torch.cat([gQ, gR, gQf, gqb], 0)
         comp["gt"] = (-2 * Qw * dX[:N, :3]).sum(0) + -2 * Qfw * dX[N, :3]
+
+    M = len(prob.obstacles)
+    gx0, gob = torch.empty(4, B, **kw), torch.empty(3 * M, B, **kw)
+    wbg = lib.dtmpc_solve_backward_geom_workspace_bytes(_abi.F32, N, B)
+    workg = torch.empty(wbg, dtype=torch.uint8, device=dev)
+    gwg, gtg = torch.empty(9, B, **kw), torch.empty(3, B, **kw)
+
+    def fused_geom():
+        _lib.check(lib.dtmpc_solve_backward_geom(_abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(),
+                                                 None, None, None, gx.data_ptr(), gu.data_ptr(), gwg.data_ptr(),
+                                                 gtg.data_ptr(), None, None, gx0.data_ptr(), gob.data_ptr(),
+                                                 workg.data_ptr(), wbg, status.data_ptr(), stream),
+                   "dtmpc_solve_backward_geom")
+
+    dL = torch.empty(N + 1, 4, B, **kw)
+    tab = torch.tensor([[o.center[0], o.center[1], o.radius] for o in prob.obstacles], **kw)
+    ocx, ocy, orr = (tab[:, j].view(1, M, 1) for j in range(3))
+    zero = torch.zeros(1, B, **kw)
+
+    def composition_geom():
+        _lib.check(lib.dtmpc_ddp_sensitivity_upper(_abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(),
+                                                   gx.data_ptr(), gu.data_ptr(), dX.data_ptr(), dU.data_ptr(),
+                                                   dL.data_ptr(), work2.data_ptr(), status.data_ptr(), stream),
+                   "dtmpc_ddp_sensitivity_upper")
+        composition_rows()
+        dx, dy = Xs[:, 0:1] - ocx, Xs[:, 1:2] - ocy  # [N+1, M, B]
+        z = -prob.obs_beta * (dx * dx + dy * dy - orr * orr)
+        w = torch.softmax(z, 1)
+        h = -torch.logsumexp(z, 1) / prob.obs_beta
+        D = barrier_and_derivative(h, kind=_abi.BARRIER_INVERSE, alpha=prob.dbas_alpha, eps=prob.dbas_eps,
+                                   want_B=False, want_dB=True)[1]
+        lam = dL[:, 3]
+        cw = (D * (torch.cat([zero, lam[1:]], 0) - prob.dbas_gamma * torch.cat([lam[1:], zero], 0)))[:, None] * w
+        comp["gx0"] = dL[0]
+        comp["gob"] = torch.cat([(cw * (-2 * dx)).sum(0), (cw * (-2 * dy)).sum(0), -cw.sum(0)], 0)  # cx, cy, r2 rows
 
     Q, R, Qf, qb = (torch.tensor(v, device=dev, requires_grad=True) for v in (cost.Q, cost.R, cost.Qf, cost.qb))
     tgt = torch.tensor(cost.target, device=dev, requires_grad=True)
@@ -106,10 +148,12 @@ def main():
         r = hold["res"]
         ((r.X * gX).sum() + (r.V * gU).sum()).backward(retain_graph=True)
 
-    ms = {k: [] for k in ("fused", "composition", "layer_forward", "layer_backward")}
+    ms = {k: [] for k in ("fused", "composition", "fused_geom", "composition_geom", "layer_forward", "layer_backward")}
     for _ in range(a.rounds):
         ms["fused"].append(timed(fused, a.reps))
         ms["composition"].append(timed(composition, a.reps))
+        ms["fused_geom"].append(timed(fused_geom, a.reps))
+        ms["composition_geom"].append(timed(composition_geom, a.reps))
         ms["layer_forward"].append(timed(layer_forward, max(a.reps // 4, 3)))
         ms["layer_backward"].append(timed(layer_backward, max(a.reps // 4, 3)))
     fused()
@@ -120,14 +164,29 @@ def main():
     # target cost: backward reads X (three fields) 12, U 8, gX 16, gU 8 and writes the 80 B record; forward reads the
     # record and X 16, U 8
     per_step = 44 + 80 + 80 + 24
+    fused_geom()
+    composition_geom()
+    torch.cuda.synchronize()
+    okg = status == 0
+    errg = {k: float(((v - comp[k]).abs().amax(0) / comp[k].abs().amax(0).clamp_min(1.0))[okg].max())
+            for k, v in (("gx0", gx0), ("gob", gob))}
+    same_old_rows = bool(torch.equal(gw.view(torch.int32), gwg.view(torch.int32)) and
+                         torch.equal(gt.view(torch.int32), gtg.view(torch.int32)))
     rec = {"B": B, "N": N, "M": len(prob.obstacles), "rounds": a.rounds, "reps": a.reps,
            "bytes_per_traj_step_by_construction": per_step,
            "bytes_per_launch_by_construction": per_step * N * B + (16 + 16 + 48) * B,
-           "flagged": int((~ok).sum()), "fused_vs_composition_max_rel": err}
+           "flagged": int((~ok).sum()), "fused_vs_composition_max_rel": err,
+           # GEOM: the record grows by 20 B written and 20 B read per step; per launch 16 B (g_x0) + 12 M B (g_obs)
+           "geom_bytes_per_traj_step_by_construction": per_step + 40,
+           "geom_bytes_per_launch_by_construction": (per_step + 40) * N * B + (16 + 16 + 48 + 16 + 12 * M + 4) * B,
+           "geom_flagged": int((~okg).sum()), "geom_fused_vs_composition_max_rel": errg,
+           "geom_old_rows_bitwise": same_old_rows}
     for n, v in ms.items():
         rec[n] = {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
                   "spread": round(max(v) - min(v), 4)}
     rec["fused_GBps_by_construction"] = round(rec["bytes_per_launch_by_construction"] / rec["fused"]["ms_median"] / 1e6, 1)
+    rec["fused_geom_GBps_by_construction"] = round(rec["geom_bytes_per_launch_by_construction"] /
+                                                   rec["fused_geom"]["ms_median"] / 1e6, 1)
     line = json.dumps(rec)
     print(line, flush=True)
     if a.out:
