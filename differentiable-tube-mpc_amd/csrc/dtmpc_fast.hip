@@ -30,7 +30,8 @@
 // this file is the tube step's translation unit; dtmpc_fast_ilqr.hip / dtmpc_fast_general.hip include it
 // for the standalone iLQR's and the general path's instantiations (their host parts below)
 #if defined(DTMPC_FAST_ILQR_TU) || defined(DTMPC_FAST_GENERAL_TU) || defined(DTMPC_FAST_ILP_TU) || \
-    defined(DTMPC_FAST_SCENES_TU) || defined(DTMPC_FAST_OWN_TU) || defined(DTMPC_FAST_LAYER_TU)
+    defined(DTMPC_FAST_SCENES_TU) || defined(DTMPC_FAST_OWN_TU) || defined(DTMPC_FAST_LAYER_TU) || \
+    defined(DTMPC_FAST_WEIGHTS_TU)
 #define DTMPC_FAST_AUX_TU 1
 #endif
 // The one-lane tube kernels (the headline's form) and the f32 two-lane ones live in their own translation units
@@ -119,6 +120,12 @@ constexpr int kScene = 256;
 // gradient row (own_update below).  The step loops are the shared form's with the six weights in per-lane registers;
 // only csrc/dtmpc_fast_own.hip instantiates it.
 constexpr int kOwn = 512;
+// kWts (f32): per-trajectory cost weights in the standalone iLQR (dtmpc_ilqr_solve_weights) -- the lane fills the nine
+// weights of its FCost from its own column of the weights array [9][B] (rows Q0 Q1 Q2 R0 R1 Qf0 Qf1 Qf2 qb, the field
+// order of FCost and the row order of dtmpc_solve_backward's g_w) instead of the kernarg block's copy (wts_c below).
+// The solver is the shared ilqr<>() with the nine weights in per-lane registers; only csrc/dtmpc_fast_weights.hip
+// instantiates it (with and without kScene).
+constexpr int kWts = 1024;
 template <int M>
 struct Obs {
   static constexpr int n = M & (kTight - 1);
@@ -128,6 +135,7 @@ struct Obs {
   static constexpr bool xasm = (M & kXasm) != 0;
   static constexpr bool scene = (M & kScene) != 0;
   static constexpr bool own = (M & kOwn) != 0;
+  static constexpr bool wts = (M & kWts) != 0;
 };
 
 // obstacle i of the table: the registers of FP, or (kReread) loaded again at each use -- through an opaque pointer
@@ -2628,6 +2636,21 @@ __device__ __forceinline__ f4 scene_tg(const real* sc, size_t nb, int i) {
   const real* q = sc + i;
   return f4{q[(size_t)(3 * n) * nb], q[(size_t)(3 * n + 1) * nb], q[(size_t)(3 * n + 2) * nb], 0.f};
 }
+// kWts: trajectory i's own cost weights -- i its index in the WHOLE batch, nb the batch, the stride of the weights rows
+// [9][B].  Nine coalesced loads (one 256 B line per row per wave); the target (and every other field) stays c's.
+__device__ __forceinline__ FCost wts_c(FCost c, const real* wt, size_t nb, int i) {
+  const real* q = wt + i;
+  c.Q0 = q[0];
+  c.Q1 = q[nb];
+  c.Q2 = q[2 * nb];
+  c.R0 = q[3 * nb];
+  c.R1 = q[4 * nb];
+  c.Qf0 = q[5 * nb];
+  c.Qf1 = q[6 * nb];
+  c.Qf2 = q[7 * nb];
+  c.qb = q[8 * nb];
+  return c;
+}
 // kOwn: trajectory i's momentum + projected update of its own column of theta / vel [6][B] from its own gradient row
 // g (acc[1..6] after the health masking: zeros for a trajectory left out, whose momentum still decays and moves
 // theta -- the shared update at B = 1 with an empty healthy set).  The roundings are theta_update_kernel<float>'s as
@@ -3026,6 +3049,9 @@ struct IArgs {
   real* work;
   unsigned wsz, oX, oU, oK, ok, oXR, oUR;
   const real* scenes;  // [3M + 3][B] or NULL (dtmpc_ilqr_solve_scenes): read by the kScene instantiations only
+  // [9][B] or NULL (dtmpc_ilqr_solve_weights): read by the kWts instantiations only.  It takes 8 of the 16 bytes of
+  // tail padding IK had (its alignment is its ext-vectors' 32), so no kernel's argument block grows or moves
+  const real* weights;
 };
 struct IK {
   FP p;
@@ -3090,7 +3116,11 @@ ilqr_fast_kernel(IK kk) {
   Prof pf;
   pf.start();
   int st;
-  if constexpr (Obs<ML>::scene && !TRACK) {  // the trajectory's own target (a tracking cost has none)
+  if constexpr (Obs<ML>::wts) {  // the trajectory's own weights, and with kScene and a target cost its own target
+    FCost cs = wts_c(c, a.weights, nb, i);
+    if constexpr (Obs<ML>::scene && !TRACK) cs.tg = scene_tg<ML>(a.scenes, nb, i);
+    st = ilqr<TRACK, ML, P, false>(p, cs, cf, x0, S, h, sm, it, pf, dr);
+  } else if constexpr (Obs<ML>::scene && !TRACK) {  // the trajectory's own target (a tracking cost has none)
     FCost cs = c;
     cs.tg = scene_tg<ML>(a.scenes, nb, i);
     st = ilqr<TRACK, ML, P, false>(p, cs, cf, x0, S, h, sm, it, pf, dr);
@@ -3467,6 +3497,10 @@ int launch_ilqr_fast_scenes(int M, int lanes, bool track, dim3 grid, unsigned bs
 // the own-theta launches (csrc/dtmpc_fast_own.hip: the kOwn instantiations of the tube step, M obstacles at the
 // gamma = 0 record form, with kScene as well when `scene`): kk.k the step's arguments, kk.o the own-theta block
 int launch_tube_fast_own(int M, int lanes, bool scene, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FKOwn& kk);
+// the per-trajectory-weights launches (csrc/dtmpc_fast_weights.hip: the kWts instantiations of the standalone iLQR, M
+// obstacles at the gamma = 0 record form, with kScene as well when `scene`): kk.a.weights set
+int launch_ilqr_fast_weights(int M, int lanes, bool track, bool scene, dim3 grid, unsigned bs, hipStream_t st,
+                             const FK_NS::IK& kk);
 #endif
 
 #ifndef DTMPC_FAST_AUX_TU  // the tube step (this file's own translation unit)
@@ -3821,11 +3855,13 @@ bool FKN(ilqr_fast_eligible)(int dtype, const dtmpc_spec* sp, const dtmpc_cost* 
 int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmpc_ilqr_cfg* cf, int64_t B, const void* x0,
                      const void* Xref, const void* Uref, void* X, void* U, void* K, void* kff, int* iters, int* status,
                      signed char* choices, void* costs, int lanes, void* work, size_t work_bytes, hipStream_t st,
-                     const void* scenes) {
+                     const void* scenes, const void* weights) {
   const int N = sp->horizon;
   if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "lanes must be 1, 2 or 4");
   if (scenes && (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0))  // dtmpc_ilqr_solve_scenes has refused these
     return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes need f32 and dbas_gamma == 0");
+  if (weights && (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0))  // dtmpc_ilqr_solve_weights has refused these
+    return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory weights need f32 and dbas_gamma == 0");
   if (!work || work_bytes < FKN(ilqr_fast_workspace_bytes)(N, B, lanes))
     return set_err(DTMPC_ERR_BAD_ARG, "work_bytes < dtmpc_ilqr_workspace_bytes(...)");
   FK_NS::IK kk;
@@ -3851,9 +3887,14 @@ int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmp
   a.costs = (real*)costs;
   a.work = (real*)work;
   a.scenes = (const real*)scenes;
+  a.weights = (const real*)weights;
   // gamma = 0: the compact gain records and the Riccati step without the barrier state's column
   const int g0 = kk.p.gamma == 0.f ? 2 : 0;
-  const int64_t chunk = FKN(ilqr_fast_chunk_max)(N, lanes);
+  int64_t chunk = FKN(ilqr_fast_chunk_max)(N, lanes);
+  if (const char* e = weights ? getenv("DTMPC_FAST_CHUNK") : nullptr) {  // a smaller launch chunk, as dtmpc_tube_chunk
+    const int64_t v = atoll(e) / kBlock * kBlock;  // takes it (the weights launches only: the trajectory index must be
+    if (v > 0 && v < chunk) chunk = v;             // the batch's in every chunk, tests/test_gpu_weights.py)
+  }
   for (int64_t c0 = 0; c0 < B; c0 += chunk) {
     const int64_t Bc = B - c0 < chunk ? B - c0 : chunk;
     const int64_t ns = lanes == 4 ? FK_NS::kSlots : 1;
@@ -3869,6 +3910,11 @@ int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmp
     const int bs = tube_block(B, lanes);
     const dim3 grid = dim3((unsigned)((Bc * lanes + bs - 1) / bs));
 #if !DTMPC_FAST_F64
+    if (a.weights) {  // per-trajectory weights (with or without scenes): the kWts kernels' unit
+      if (int r = launch_ilqr_fast_weights(sp->n_obstacles, lanes, track, a.scenes != nullptr, grid, (unsigned)bs, st, kk))
+        return r;
+      continue;
+    }
     if (a.scenes) {  // per-trajectory scenes: the kScene kernels' unit
       if (int r = launch_ilqr_fast_scenes(sp->n_obstacles, lanes, track, grid, (unsigned)bs, st, kk)) return r;
       continue;
@@ -4060,6 +4106,34 @@ int launch_tube_fast_own(int M, int lanes, bool scene, dim3 grid, unsigned bs, h
 #undef OWN_CASE
 #undef OWN_LANES
 #undef OWN_LAUNCH
+}
+
+#elif defined(DTMPC_FAST_WEIGHTS_TU)  // the per-trajectory-weights iLQR kernels (csrc/dtmpc_fast_weights.hip), f32 only
+
+int launch_ilqr_fast_weights(int M, int lanes, bool track, bool scene, dim3 grid, unsigned bs, hipStream_t st,
+                             const FK_NS::IK& kk) {
+#define WT_LAUNCH(m, l, t) hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<(m), l, t, 2>), grid, dim3(bs), 0, st, kk)
+#define WT_T(m, l) \
+  if (track) WT_LAUNCH(m, l, true); else WT_LAUNCH(m, l, false);
+#define WT_LANES(m) \
+  if (lanes == 4) { WT_T(m, 4) } else if (lanes == 2) { WT_T(m, 2) } else { WT_T(m, 1) }
+#define WT_CASE(m) \
+  case m:          \
+    if (scene) { WT_LANES(m | FK_NS::kWts | FK_NS::kScene) } else { WT_LANES(m | FK_NS::kWts) } \
+    return 0;
+  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "weights iLQR unit: lanes");
+  switch (M) {
+#ifdef DTMPC_FAST_M_ONLY
+    WT_CASE(DTMPC_FAST_M_ONLY)
+#else
+    WT_CASE(1) WT_CASE(2) WT_CASE(3) WT_CASE(4) WT_CASE(5) WT_CASE(6) WT_CASE(7) WT_CASE(8)
+#endif
+    default: return set_err(DTMPC_ERR_BAD_ARG, "fast iLQR with weights: obstacle count not instantiated");
+  }
+#undef WT_CASE
+#undef WT_LANES
+#undef WT_T
+#undef WT_LAUNCH
 }
 
 #elif defined(DTMPC_FAST_LAYER_TU)  // the differentiable solve's backward (csrc/dtmpc_fast_layer.hip), f32 only

@@ -22,7 +22,9 @@
 // GEOM variant (dtmpc_solve_backward_geom, solve_backward_geom_kernel): the two terms that DO involve delta_lambda, the
 // rows w.r.t. the start state (g_x0 = tilde V_x[0]) and the obstacle circles.  It keeps the barrier row of V_xx and of
 // tilde V_x per step as well (25 values, 100 B), forms lam_k in the forward sweep and accumulates 3M sums (geom_row).
-// Both kernels include one body text, dtmpc_fast_layer_body.hpp.
+// WTS variant (dtmpc_solve_backward_weights, solve_backward_weights_kernel<M, TRACK, GEOM>): the nine cost weights per
+// trajectory, from a weights array [9][B] (36 B more read per trajectory); one kernel family for both record forms.
+// All kernels include one body text, dtmpc_fast_layer_body.hpp.
 #define DTMPC_FAST_LAYER_TU 1
 #include "dtmpc_fast.hip"
 
@@ -112,17 +114,38 @@ __device__ __forceinline__ void geom_row(const FP& p, real px, real py, real co,
 template <int M, bool TRACK>
 __global__ void __launch_bounds__(kBlock) solve_backward_kernel(LK kk) {
   constexpr bool GEOM = false;
+  constexpr bool WTS = false;
   real* const gx0 = nullptr;
   real* const gob = nullptr;
+  const real* const wts = nullptr;
+  (void)wts;
 #include "dtmpc_fast_layer_body.hpp"
 }
 // ... and with the rows w.r.t. the start state and the obstacle circles (dtmpc_solve_backward_geom)
 template <int M, bool TRACK>
 __global__ void __launch_bounds__(kBlock) solve_backward_geom_kernel(LKG kg) {
   constexpr bool GEOM = true;
+  constexpr bool WTS = false;
   const LK& kk = kg.k;
   real* const gx0 = kg.gx0;
   real* const gob = kg.gob;
+  const real* const wts = nullptr;
+  (void)wts;
+#include "dtmpc_fast_layer_body.hpp"
+}
+// ... and with per-trajectory cost weights (dtmpc_solve_backward_weights): both record forms, G the GEOM one
+struct LKW {
+  LKG g;            // p first
+  const real* wts;  // [9][B]: rows Q0 Q1 Q2 R0 R1 Qf0 Qf1 Qf2 qb (g_w's row order)
+};
+template <int M, bool TRACK, bool G>
+__global__ void __launch_bounds__(kBlock) solve_backward_weights_kernel(LKW kw) {
+  constexpr bool GEOM = G;
+  constexpr bool WTS = true;
+  const LK& kk = kw.g.k;
+  real* const gx0 = kw.g.gx0;
+  real* const gob = kw.g.gob;
+  const real* const wts = kw.wts;
 #include "dtmpc_fast_layer_body.hpp"
 }
 
@@ -147,10 +170,13 @@ static size_t layer_workspace_bytes(int32_t N, int64_t B, bool geom = false) {
 
 // geom: solve_backward_geom_kernel with the two further outputs (either may be NULL), else solve_backward_kernel
 static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int64_t B, const fk::LArgs& a,
-                                 hipStream_t st, bool geom = false, real* gx0 = nullptr, real* gob = nullptr) {
-  fk::LKG kg;
-  std::memset(&kg, 0, sizeof(kg));
+                                 hipStream_t st, bool geom = false, real* gx0 = nullptr, real* gob = nullptr,
+                                 const real* wts = nullptr) {
+  fk::LKW kw;
+  std::memset(&kw, 0, sizeof(kw));
+  fk::LKG& kg = kw.g;
   fk::LK& kk = kg.k;
+  kw.wts = wts;
   fast_p(sp, kk.p);
   const DCost<real> c = make_cost<real>(*cp);
   const bool track = cp->kind == DTMPC_COST_TRACK;
@@ -170,7 +196,18 @@ static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int
 #else
 #define LY_CASES LY_CASE(1) LY_CASE(2) LY_CASE(3) LY_CASE(4) LY_CASE(5) LY_CASE(6) LY_CASE(7) LY_CASE(8)
 #endif
-  if (!geom) {
+  if (wts) {  // per-trajectory weights: one family for both record forms
+#define LY_LAUNCH(m, t)                                                                                       \
+  do {                                                                                                        \
+    if (geom) hipLaunchKernelGGL((fk::solve_backward_weights_kernel<m, t, true>), grid, dim3(bs), 0, st, kw); \
+    else hipLaunchKernelGGL((fk::solve_backward_weights_kernel<m, t, false>), grid, dim3(bs), 0, st, kw);     \
+  } while (0)
+    switch (sp->n_obstacles) {
+      LY_CASES
+      default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
+    }
+#undef LY_LAUNCH
+  } else if (!geom) {
 #define LY_LAUNCH(m, t) hipLaunchKernelGGL((fk::solve_backward_kernel<m, t>), grid, dim3(bs), 0, st, kk)
     switch (sp->n_obstacles) {
       LY_CASES
@@ -187,7 +224,7 @@ static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int
   }
 #undef LY_CASES
 #undef LY_CASE
-  return check_launch(geom ? "solve_backward_geom_kernel" : "solve_backward_kernel");
+  return check_launch(wts ? "solve_backward_weights_kernel" : geom ? "solve_backward_geom_kernel" : "solve_backward_kernel");
 }
 
 // dtmpc_solve_backward and dtmpc_solve_backward_geom: the argument rules of include/dtmpc.h, then the launch
@@ -195,7 +232,7 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
                                 const void* X, const void* U, const void* Xref, const void* Uref, const void* scenes,
                                 const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
                                 void* g_x0, void* g_obs, void* work, size_t work_bytes, int32_t* status,
-                                void* stream) {
+                                void* stream, bool wts = false, const void* weights = nullptr) {
   if (!spec || !cost) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL spec or cost");
   if (B < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: batch must be >= 1");
   if (spec->horizon < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: horizon must be >= 1");
@@ -205,7 +242,8 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
   if (const char* why = layer_unsupported(dtype, spec, cost)) return set_err(DTMPC_ERR_BAD_ARG, why);
   if (!X || !U || !gX || !gU || !g_w || !status)
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL X, U, gX, gU, g_w or status");
-  if (geom && !g_x0 && !g_obs)
+  if (wts && !weights) return set_err(DTMPC_ERR_BAD_ARG, "solve backward weights: NULL weights");
+  if (geom && !wts && !g_x0 && !g_obs)
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward geom: g_x0 and g_obs both NULL (that is dtmpc_solve_backward)");
   if (cost->kind == DTMPC_COST_TRACK) {
     if (!Xref || !Uref) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: the tracking cost needs Xref and Uref");
@@ -214,7 +252,9 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward: Xref, Uref, g_xref and g_uref go with the tracking cost");
   }
   if (!work || work_bytes < layer_workspace_bytes(spec->horizon, B, geom))
-    return set_err(DTMPC_ERR_BAD_ARG, geom ? "solve backward geom: work_bytes < "
+    return set_err(DTMPC_ERR_BAD_ARG, wts  ? "solve backward weights: work_bytes < "
+                                             "dtmpc_solve_backward_weights_workspace_bytes(...)"
+                                      : geom ? "solve backward geom: work_bytes < "
                                              "dtmpc_solve_backward_geom_workspace_bytes(...)"
                                            : "solve backward: work_bytes < dtmpc_solve_backward_workspace_bytes(...)");
   fk::LArgs a;
@@ -232,7 +272,8 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
   a.gur = (real*)g_uref;
   a.work = (real*)work;
   a.status = status;
-  return launch_solve_backward(spec, cost, B, a, (hipStream_t)stream, geom, (real*)g_x0, (real*)g_obs);
+  return launch_solve_backward(spec, cost, B, a, (hipStream_t)stream, geom, (real*)g_x0, (real*)g_obs,
+                               (const real*)weights);
 }
 
 }  // namespace dtmpc
@@ -267,6 +308,21 @@ int dtmpc_solve_backward_geom(int dtype, const dtmpc_spec* spec, const dtmpc_cos
                               void* g_obs, void* work, size_t work_bytes, int32_t* status, void* stream) {
   return dtmpc::solve_backward_entry(true, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
                                      g_uref, g_x0, g_obs, work, work_bytes, status, stream);
+}
+
+size_t dtmpc_solve_backward_weights_workspace_bytes(int dtype, int32_t horizon, int64_t B, int32_t geom) {
+  if (dtype != DTMPC_F32 || horizon < 1 || B < 1) return 0;
+  return dtmpc::layer_workspace_bytes(horizon, B, geom != 0);
+}
+
+int dtmpc_solve_backward_weights(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B, const void* X,
+                                 const void* U, const void* Xref, const void* Uref, const void* scenes,
+                                 const void* weights, const void* gX, const void* gU, void* g_w, void* g_target,
+                                 void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* work, size_t work_bytes,
+                                 int32_t* status, void* stream) {
+  // the GEOM record (25 values) when either of its outputs is asked for, else the plain one (20)
+  return dtmpc::solve_backward_entry(g_x0 || g_obs, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target,
+                                     g_xref, g_uref, g_x0, g_obs, work, work_bytes, status, stream, true, weights);
 }
 
 }  // extern "C"

@@ -3,7 +3,10 @@
 // GEOM, the two further outputs gx0 / gob.  Text, not a shared device function: with GEOM false every `if constexpr
 // (GEOM)` statement is discarded in the front end and the kernel's code is what it was before the variant existed
 // (a body shared through a reference to the kernel's argument compiled to other code, ten VGPRs more).
-// No include guard: it is included twice on purpose.
+// WTS (solve_backward_weights_kernel, dtmpc_solve_backward_weights): a third constexpr bool beside GEOM, with the
+// pointer `wts` -- the nine cost weights come from the lane's own column of the weights array [9][B] (wts_c) instead of
+// kk.c, so g_xref = -2 Q_i dx and g_target use trajectory i's own Q / Qf; with WTS false the statement is discarded.
+// No include guard: it is included three times on purpose.
   constexpr int REC = GEOM ? kGeomRec : kLayerRec;
   using LFwd = typename std::conditional<GEOM && (M > 0), LFwdInG, LFwdIn>::type;  // (M > 0: a dependent type)
   const LArgs& a = kk.a;
@@ -12,6 +15,7 @@
   const size_t nb = (size_t)a.B;
   FP p = kk.p;
   FCost c = kk.c;
+  if constexpr (WTS) c = wts_c(c, wts, nb, i);  // this trajectory's own weights
   if (a.sc) {  // per-trajectory scene: this trajectory's obstacles and, for the target cost, its target
     p = scene_p<M>(p, a.sc, nb, i);
     if (!TRACK) c.tg = scene_tg<M>(a.sc, nb, i);

@@ -255,6 +255,19 @@ PROTOTYPES = {
         [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
          C.c_size_t, P, P],
     ),
+    # per-trajectory cost weights [9][B] (beside ABI 8)
+    "dtmpc_weights_supported": (I32, [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcIlqrCfg)]),
+    "dtmpc_ilqr_solve_weights": (
+        C.c_int,
+        [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), C.POINTER(DtmpcIlqrCfg), I64, P, P, P, P, P, P, P, P, P, P,
+         P, I32, P, C.c_size_t, P, P, P],
+    ),
+    "dtmpc_solve_backward_weights_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64, I32]),
+    "dtmpc_solve_backward_weights": (
+        C.c_int,
+        [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+         C.c_size_t, P, P],
+    ),
     "dtmpc_sensitivity_upper_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64]),
     "dtmpc_ddp_sensitivity_upper": (
         C.c_int,

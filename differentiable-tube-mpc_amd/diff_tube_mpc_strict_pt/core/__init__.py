@@ -28,6 +28,7 @@ from .problem import (
     QuadraticCost,
     general_setup_from_config,
     pack_scenes,
+    pack_weights,
     paper_setup_from_config,
     problem_from_config,
     tracking_cost,
@@ -80,6 +81,7 @@ __all__ = [
     "ilqr_solve",
     "linearize",
     "pack_scenes",
+    "pack_weights",
     "paper_setup_from_config",
     "problem_from_config",
     "raise_for_status",

@@ -28,7 +28,7 @@ import torch
 from torch import Tensor
 
 from .. import _abi, _lib
-from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes
+from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, check_weights
 
 __all__ = [
     "ILQRConfig",
@@ -191,7 +191,7 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
                cfg: ILQRConfig, x0: Tensor, V_init: Tensor, X_ref: Optional[Tensor] = None,
                U_ref: Optional[Tensor] = None, check: bool = True, debug_name: str = "ilqr",
                record_choices: bool = False, lanes: int = 0, record_costs: bool = False,
-               scenes: Optional[Tensor] = None,
+               scenes: Optional[Tensor] = None, weights: Optional[Tensor] = None,
                f=None, f_jac=None, ctrl=None, stage_cost=None, terminal_cost=None, stage_derivs=None,
                terminal_derivs=None, feasible_fn=None, debug: bool = False):
     """Batched box-clamped iLQR (core/ddp.py:102-307).
@@ -211,10 +211,15 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
     (dtmpc_ilqr_fused_eligible says which).
     scenes ([3M + 3, B], problem.pack_scenes): trajectory i solves with its own obstacles and -- for the target
     cost -- its own target (``cost.target`` is then unused); fused f32 solver only, ValueError where
-    dtmpc_scenes_supported says no."""
+    dtmpc_scenes_supported says no.
+    weights ([9, B] float32, problem.pack_weights): trajectory i solves with its own Q, R, Qf, qb (``cost``'s nine
+    weights are then unused; its kind, target and wrap_angle hold); composes with ``scenes``; fused f32 solver only,
+    ValueError where dtmpc_weights_supported says no -- never the shared weights instead."""
     if f is not None:
         if scenes is not None:
             raise TypeError("scenes go with the typed form (problem / cost)")
+        if weights is not None:
+            raise TypeError("weights go with the typed form (problem / cost)")
         if problem is not None or cost is not None:
             raise TypeError("pass either problem / cost (typed form) or the closures (keyword form), not both")
         from .closures import resolve_ilqr
@@ -240,6 +245,16 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
     lib = _lib.load()
     spec, cc, ic = problem.to_c(), cost.to_c(), cfg.to_c()
     dt = x0.dtype
+    if weights is not None:  # refused before anything runs; never the shared weights instead
+        if dt != torch.float32 or not lib.dtmpc_weights_supported(_dtype_code(x0), C.byref(spec), C.byref(ic)) \
+                or cost.wrap_angle:
+            raise ValueError("per-trajectory weights are not supported for this dtype / problem / line search "
+                             "(dtmpc_weights_supported: f32, smooth-min, 1..8 obstacles, inverse barrier, gamma = 0, "
+                             "six non-zero alphas, DTMPC_FAST != 0, no wrapped heading error)")
+        _require_device(weights, scenes)
+        check_weights(weights, B, x0.device)
+        if scenes is not None:
+            check_scenes(scenes, len(problem.obstacles), B, dt, x0.device)
     x0s = _prep_x0(x0)
     Us = to_soa(V_init.to(dt))
     Xr = to_soa(X_ref[..., :3].to(dt)) if X_ref is not None else None
@@ -257,7 +272,14 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
         raise ValueError("lanes must be 0 (default), 1, 2 or 4")
     wb = int(lib.dtmpc_ilqr_workspace_bytes(_dtype_code(x0), N, B, lanes))
     work = torch.empty(max(wb, 1), dtype=torch.uint8, device=x0.device)
-    if scenes is not None:
+    if weights is not None:
+        _lib.check(lib.dtmpc_ilqr_solve_weights(_dtype_code(x0), C.byref(spec), C.byref(cc), C.byref(ic), B,
+                                                x0s.data_ptr(), _ptr(Xr), _ptr(Ur), Xs.data_ptr(), Us.data_ptr(),
+                                                Ks.data_ptr(), ks.data_ptr(), iters.data_ptr(), status.data_ptr(),
+                                                _ptr(ch), _ptr(cr), lanes, work.data_ptr(), wb, _ptr(scenes),
+                                                weights.data_ptr(), _lib.stream_of(x0)),
+                   "dtmpc_ilqr_solve_weights")
+    elif scenes is not None:
         _require_device(scenes)
         check_scenes(scenes, len(problem.obstacles), B, dt, x0.device)
         if not lib.dtmpc_scenes_supported(_dtype_code(x0), C.byref(spec), C.byref(ic)) or cost.wrap_angle:

@@ -37,7 +37,7 @@ from .. import _abi, _lib
 from .barrier import barrier_and_derivative
 from .ddp import (ILQRResult, _ddp_sensitivity_upper, _dtype_code, _ptr, _require_device, from_soa, ilqr_solve,
                   raise_for_status, to_soa)
-from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, pack_scenes
+from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, check_weights, pack_scenes, pack_weights
 
 __all__ = ["SolveGradient", "solve_backward", "diff_ilqr_solve"]
 
@@ -87,7 +87,7 @@ def _obstacle_rows(problem: DubinsDBaSProblem, X: Tensor, dlam: Tensor) -> Tenso
 def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor, V: Tensor, grad_X: Tensor,
                    grad_V: Tensor, X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
                    scenes: Optional[Tensor] = None, check: bool = True, want_x0: bool = False,
-                   want_obstacles: bool = False) -> SolveGradient:
+                   want_obstacles: bool = False, weights: Optional[Tensor] = None) -> SolveGradient:
     """The gradient of an upper loss w.r.t. the plain cost weights and the references, per trajectory, from the
     loss's gradients ``grad_X`` [B, N+1, 4] / ``grad_V`` [B, N, 2] w.r.t. the tape (X [B, N+1, 4], V [B, N, 2]).
 
@@ -103,11 +103,16 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
     want_x0 / want_obstacles: also the rows w.r.t. the start state (``x0`` [B, 4]: x, y, heading, b) and the circles
     (``obstacles`` [B, M, 3]: cx, cy, r -- trajectory i's own circles with scenes, whose radii are the roots of the
     scene's squared radii).  x0 rows come on every path; obstacle rows need smooth-min aggregation and the relaxed
-    inverse barrier (the fused kernel, or on f64 the composition without scenes)."""
+    inverse barrier (the fused kernel, or on f64 the composition without scenes).
+
+    weights ([9, B] float32, pack_weights): trajectory i is differentiated with its own Q, R, Qf, qb (``cost``'s nine
+    weights are then unused), so ``X_ref`` / ``target`` rows carry its own Q / Qf and row i of ``weights`` in the
+    result is the gradient w.r.t. column i of the array.  Fused f32 kernel only (dtmpc_solve_backward_weights, any
+    dbas_gamma): the composition paths (f64, min / single aggregation, the log barrier) raise ValueError."""
     if cost.wrap_angle:
         raise ValueError("solve_backward: a cost with wrap_angle is not supported (the reference's sensitivity "
                          "closures carry no wrapped heading error)")
-    _require_device(X, V, grad_X, grad_V, X_ref, U_ref, scenes)
+    _require_device(X, V, grad_X, grad_V, X_ref, U_ref, scenes, weights)
     B, N = X.shape[0], problem.horizon
     if X.shape != (B, N + 1, 4) or V.shape != (B, N, 2):
         raise ValueError(f"X must be [B, {N + 1}, 4] and V [B, {N}, 2]")
@@ -128,6 +133,8 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
     if fused:
         if scenes is not None:
             check_scenes(scenes, M, B, dt, dev)
+        if weights is not None:
+            check_weights(weights, B, dev)
         Xs, Us, gx, gu = to_soa(X), to_soa(V.to(dt)), to_soa(grad_X.to(dt)), to_soa(grad_V.to(dt))
         Xr = to_soa(X_ref[..., :3].to(dt)) if track else None
         Ur = to_soa(U_ref.to(dt)) if track else None
@@ -137,14 +144,21 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         gur = torch.empty(N, 2, B, **kw) if track else None
         gx0 = torch.empty(4, B, **kw) if want_x0 else None
         gob = torch.empty(3, M, B, **kw) if want_obstacles else None
-        nbytes = lib.dtmpc_solve_backward_geom_workspace_bytes if geom else lib.dtmpc_solve_backward_workspace_bytes
-        wb = int(nbytes(_dtype_code(X), N, B))
+        if weights is not None:
+            wb = int(lib.dtmpc_solve_backward_weights_workspace_bytes(_dtype_code(X), N, B, 1 if geom else 0))
+        else:
+            nbytes = (lib.dtmpc_solve_backward_geom_workspace_bytes if geom
+                      else lib.dtmpc_solve_backward_workspace_bytes)
+            wb = int(nbytes(_dtype_code(X), N, B))
         work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
         head = (_dtype_code(X), C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), _ptr(Xr), _ptr(Ur),
                 _ptr(scenes), gx.data_ptr(), gu.data_ptr(), gw.data_ptr(), _ptr(gt), _ptr(gxr), _ptr(gur))
         tail = (work.data_ptr(), wb, status.data_ptr(), _lib.stream_of(X))
-        if geom:  # the GEOM variant of the kernel: the same rows, and those w.r.t. x0 / (cx, cy, r^2)
+        if weights is not None:  # the WTS family: the plain record, or the GEOM one when x0 / obstacle rows are wanted
+            _lib.check(lib.dtmpc_solve_backward_weights(*head[:9], weights.data_ptr(), *head[9:], _ptr(gx0), _ptr(gob),
+                                                        *tail), "dtmpc_solve_backward_weights")
+        elif geom:  # the GEOM variant of the kernel: the same rows, and those w.r.t. x0 / (cx, cy, r^2)
             _lib.check(lib.dtmpc_solve_backward_geom(*head, _ptr(gx0), _ptr(gob), *tail), "dtmpc_solve_backward_geom")
         else:
             _lib.check(lib.dtmpc_solve_backward(*head, *tail), "dtmpc_solve_backward")
@@ -159,6 +173,9 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
                             X_ref=from_soa(gxr) if track else None, U_ref=from_soa(gur) if track else None,
                             status=status, x0=gx0.t().contiguous() if want_x0 else None, obstacles=rows)
     else:
+        if weights is not None:
+            raise ValueError("solve_backward: per-trajectory weights need the fused kernel "
+                             "(dtmpc_solve_backward_supported: f32, smooth-min, 1..8 obstacles, inverse barrier)")
         if scenes is not None:
             raise ValueError("solve_backward: per-trajectory scenes need the fused kernel "
                              "(dtmpc_solve_backward_supported: f32, smooth-min, 1..8 obstacles, inverse barrier)")
@@ -204,8 +221,9 @@ class _Solve(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, V, problem, cost, scenes, per_traj_target, nref, Q, R, Qf, qb, target, X_ref, U_ref,
-                x0=None, obstacles=None):
+                x0=None, obstacles=None, weights=None):
         ctx.problem, ctx.cost, ctx.scenes = problem, cost, scenes
+        ctx.weights = weights  # [9, B] packed (detached) or None: Q, R, Qf, qb are then [B, .] and get their rows
         ctx.per_traj_target, ctx.nref = per_traj_target, nref
         ctx.shapes = tuple(None if t is None else (t.shape, t.dtype)
                            for t in (Q, R, Qf, qb, target, X_ref, U_ref, x0, obstacles))
@@ -223,7 +241,8 @@ class _Solve(torch.autograd.Function):
         need = ctx.needs_input_grad[7:]
         g = solve_backward(problem=ctx.problem, cost=ctx.cost, X=X, V=V, grad_X=gX.contiguous(),
                            grad_V=gV.contiguous(), X_ref=None if Xr is None else Xr.detach(),
-                           U_ref=None if Ur is None else Ur.detach(), scenes=ctx.scenes, check=False,
+                           U_ref=None if Ur is None else Ur.detach(), scenes=ctx.scenes, weights=ctx.weights,
+                           check=False,
                            want_x0=sh[7] is not None and need[7], want_obstacles=sh[8] is not None and need[8])
         keep = (g.status == 0)
         ctx.flagged = g.status  # [B] int32: the trajectories left out of this backward
@@ -232,11 +251,11 @@ class _Solve(torch.autograd.Function):
             return None if t is None else torch.where(keep.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros_like(t))
 
         w = rows(g.weights)
-        ws = w.sum(0)
+        ws = w if ctx.weights is not None else w.sum(0)  # per-trajectory weights: the rows, unsummed
         out = [None] * 9
         for j, sl in enumerate((slice(0, 3), slice(3, 5), slice(5, 8), slice(8, 9))):
             if sh[j] is not None and need[j]:
-                out[j] = ws[sl].reshape(sh[j][0]).to(sh[j][1])
+                out[j] = ws[..., sl].reshape(sh[j][0]).to(sh[j][1])
         if sh[4] is not None and need[4] and g.target is not None:
             t = rows(g.target)
             out[4] = (t if ctx.per_traj_target else t.sum(0)).reshape(sh[4][0]).to(sh[4][1])
@@ -252,7 +271,7 @@ class _Solve(torch.autograd.Function):
         if g.obstacles is not None:  # [M, 3]: the shared circles get the sum over the batch
             o = rows(g.obstacles)
             out[8] = (o.sum(0) if len(sh[8][0]) == 2 else o).to(sh[8][1])
-        return (None,) * 7 + tuple(out)
+        return (None,) * 7 + tuple(out) + (None,)
 
 
 @dataclass(frozen=True)
@@ -273,6 +292,12 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
                     wrt: Sequence[str] = ()) -> ILQRResult:
     """``ilqr_solve`` whose X* / V* are differentiable w.r.t. Q [3], R [2], Qf [3], qb [], the target ([3] shared
     or [B, 3] per trajectory; kind 'target') and X_ref [B, N+1, >=3] / U_ref [B, N, 2] (kind 'track').
+
+    Per-trajectory weights: each of Q, R, Qf may also be [B, k] and qb [B].  With all four shared the path is the
+    shared one, unchanged; with any of them per trajectory the shared ones are expanded, the solve runs
+    ``ilqr_solve(weights=)`` and the backward ``solve_backward(weights=)``: a [B, k] tensor's ``.grad`` is its rows,
+    unsummed, a shared one's the column sum.  float32 on a configuration ``dtmpc_weights_supported`` accepts
+    (dbas_gamma == 0 among the rest), else ValueError.
 
     Forward is exactly ``ilqr_solve`` (the same kernels, bitwise the same X*, V*): with a [B, 3] target or
     ``obstacles`` [B, M, 3] it runs ``ilqr_solve(..., scenes=pack_scenes(...))``.  The QuadraticCost is built from
@@ -315,9 +340,21 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
         if isinstance(getattr(problem, name), Tensor):
             raise ValueError(f"diff_ilqr_solve: problem.{name} must be a float -- gradients w.r.t. the DBaS "
                              "parameters remain ift_gradient's")
+    B, N = x0.shape[0], problem.horizon
+    # the weights' shapes (before anything needs a device): all four shared -- today's path -- or any per trajectory
+    # (a one-element qb beside 1-D Q, R, Qf is the shared form, as it always was)
+    shared_w = not (Q.dim() == 2 or R.dim() == 2 or Qf.dim() == 2 or (qb.dim() == 1 and qb.numel() != 1))
+    if shared_w:
+        if Q.shape != (3,) or R.shape != (2,) or Qf.shape != (3,) or qb.numel() != 1:
+            raise ValueError("Q [3], R [2], Qf [3], qb [] (shared weights)")
+    else:
+        for name, t, k in (("Q", Q, 3), ("R", R, 2), ("Qf", Qf, 3)):
+            if tuple(t.shape) not in ((k,), (B, k)):
+                raise ValueError(f"{name} must be [{k}] (shared) or [{B}, {k}] (per trajectory), got {tuple(t.shape)}")
+        if tuple(qb.shape) not in ((), (B,)):
+            raise ValueError(f"qb must be [] (shared) or [{B}] (per trajectory), got {tuple(qb.shape)}")
     _require_device(x0, V_init, Q, R, Qf, qb, target, X_ref, U_ref,
                     obstacles if isinstance(obstacles, Tensor) else None)
-    B, N = x0.shape[0], problem.horizon
     track = kind == "track"
     if track and (X_ref is None or U_ref is None):
         raise ValueError("kind 'track' needs X_ref and U_ref")
@@ -327,14 +364,24 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
         raise ValueError("X_ref / U_ref go with kind 'track'")
     if not track and target is None:
         raise ValueError("kind 'target' needs target ([3] or [B, 3])")
-    if Q.shape != (3,) or R.shape != (2,) or Qf.shape != (3,) or qb.numel() != 1:
-        raise ValueError("Q [3], R [2], Qf [3], qb [] (shared weights)")
     per_traj = (not track) and target.dim() == 2
     if not track and tuple(target.shape) not in ((3,), (B, 3)):
         raise ValueError(f"target must be [3] or [{B}, 3]")
+    wts = None
+    if not shared_w:
+        # per-trajectory weights: the shared ones expanded to [B, .] OUTSIDE the autograd Function (autograd sums their
+        # rows), the packed array to the kWts kernels; the QuadraticCost below keeps trajectory 0's values, unread
+        if x0.dtype != torch.float32:
+            raise ValueError("diff_ilqr_solve: per-trajectory weights need float32 (dtmpc_weights_supported)")
+        Q = Q if Q.dim() == 2 else Q.expand(B, 3)
+        R = R if R.dim() == 2 else R.expand(B, 2)
+        Qf = Qf if Qf.dim() == 2 else Qf.expand(B, 3)
+        qb = qb if qb.dim() == 1 else qb.expand(B)
+        wts = pack_weights(Q, R, Qf, qb, device=x0.device)
     # one device-to-host read: the ABI's cost weights are host doubles
-    host = torch.cat([t.detach().reshape(-1).to(torch.float64) for t in
-                      (Q, R, Qf, qb) + ((target,) if (not track and not per_traj) else ())]).cpu().tolist()
+    host = torch.cat([t.detach().reshape(-1)[:k].to(torch.float64) for t, k in
+                      ((Q, 3), (R, 2), (Qf, 3), (qb, 1)) + (((target, 3),) if (not track and not per_traj) else ())]
+                     ).cpu().tolist()
     cost = QuadraticCost(kind=kind, Q=tuple(host[0:3]), R=tuple(host[3:5]), Qf=tuple(host[5:8]), qb=host[8],
                          target=tuple(host[9:12]) if len(host) > 9 else (0.0, 0.0, 0.0))
     scenes = None
@@ -349,10 +396,11 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
         scenes = pack_scenes(problem, obs, tg, dtype=x0.dtype, device=x0.device)
     res = ilqr_solve(problem=problem, cost=cost, cfg=cfg, x0=x0.detach(), V_init=V_init,
                      X_ref=None if X_ref is None else X_ref.detach(), U_ref=None if U_ref is None else U_ref.detach(),
-                     check=check, debug_name="diff_ilqr_solve", lanes=lanes, scenes=scenes)
+                     check=check, debug_name="diff_ilqr_solve", lanes=lanes, scenes=scenes,
+                     **({} if wts is None else {"weights": wts}))
     nref = 0 if X_ref is None else X_ref.shape[-1]
     Xd, Vd = _Solve.apply(res.X, res.V, problem, cost, scenes, per_traj, nref, Q, R, Qf, qb, target, X_ref, U_ref,
-                          x0 if wrt_x0 else None, obstacles if wrt_obs else None)
+                          x0 if wrt_x0 else None, obstacles if wrt_obs else None, wts)
     fields = {f.name: getattr(res, f.name) for f in dataclasses.fields(ILQRResult)}
     fields.update(X=Xd, V=Vd)
     return DiffILQRResult(**fields, _node=Xd.grad_fn)

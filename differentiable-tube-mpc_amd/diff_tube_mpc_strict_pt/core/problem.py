@@ -320,6 +320,54 @@ def check_scenes(scenes, M: int, B: int, dtype, device) -> None:
         raise ValueError("scenes must be contiguous")
 
 
+def pack_weights(Q, R, Qf, qb, device=None):
+    """Per-trajectory cost weights for ``ilqr_solve(weights=)`` and ``solve_backward(weights=)``.
+
+    Q [B, 3], R [B, 2], Qf [B, 3], qb [B] (tensors or arrays).  Returns the [9, B] float32 contiguous tensor of
+    include/dtmpc.h ("per-trajectory cost weights"): rows Q0 Q1 Q2 R0 R1 Qf0 Qf1 Qf2 qb -- the row order of
+    ``SolveGradient.weights``' columns -- each value rounded to float32 once, as the library rounds a QuadraticCost's
+    host doubles, so B copies of a cost's weights give bitwise the shared path's results.  The QuadraticCost passed
+    beside the array still supplies the kind, the target and wrap_angle; its nine weights are not read."""
+    import torch
+
+    def f32(a):
+        if isinstance(a, torch.Tensor):
+            return a.detach().to(device=a.device if device is None else device, dtype=torch.float32)
+        import numpy as np
+
+        return torch.from_numpy(np.array(a, dtype=np.float64)).to(device=device, dtype=torch.float32)
+
+    q, r, qf, b = f32(Q), f32(R), f32(Qf), f32(qb)
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError("Q must be [B, 3]")
+    B = q.shape[0]
+    if B < 1:
+        raise ValueError("empty batch")
+    if tuple(r.shape) != (B, 2) or tuple(qf.shape) != (B, 3) or tuple(b.shape) != (B,):
+        raise ValueError(f"R must be [{B}, 2], Qf [{B}, 3] and qb [{B}]")
+    w = torch.cat([q.t(), r.t(), qf.t(), b[None]], 0).contiguous()  # [9, B]
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("weights must be finite")
+    return w
+
+
+def check_weights(weights, B: int, device, finite: bool = True) -> None:
+    """The shape / dtype / placement contract of a packed weights tensor (the kernels index it unchecked), and its
+    finiteness (one device-to-host read; ``finite=False`` skips it)."""
+    import torch
+
+    if weights.dim() != 2 or tuple(weights.shape) != (9, B):
+        raise ValueError(f"weights must be [9, {B}] (pack_weights), got {tuple(weights.shape)}")
+    if weights.dtype != torch.float32:
+        raise ValueError(f"weights must be torch.float32, got {weights.dtype}")
+    if weights.device.type != device.type or (device.index is not None and weights.device.index != device.index):
+        raise ValueError(f"weights must live on {device}, got {weights.device}")
+    if not weights.is_contiguous():
+        raise ValueError("weights must be contiguous")
+    if finite and not bool(torch.isfinite(weights).all()):
+        raise ValueError("weights must be finite")
+
+
 def tracking_cost(theta: Sequence[float]) -> QuadraticCost:
     """Ancillary tracking cost with weights theta = (Qa, Ra, qba); terminal weight Qa
     (core/tube_mpc.py:875-894)."""

@@ -500,6 +500,44 @@ int dtmpc_solve_backward_geom(int dtype, const dtmpc_spec* spec, const dtmpc_cos
                               const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
                               void* g_x0, void* g_obs, void* work, size_t work_bytes, int32_t* status, void* stream);
 
+/* ---- per-trajectory cost weights in the standalone solve and its backward ------------------ */
+/*
+ * `weights` is SoA [9][B] f32: rows Q0 Q1 Q2 R0 R1 Qf0 Qf1 Qf2 qb -- the row order of g_w -- element (row, i) at
+ * row * B + i.  Trajectory i solves (and is differentiated) with the weights of column i; the dtmpc_cost passed
+ * beside the array still supplies the kind, the target and wrap_angle, its nine weights are not read.  The fused f32
+ * kernels read a lane's column into registers once (csrc/dtmpc_fast_weights.hip, solve_backward_weights_kernel in
+ * csrc/dtmpc_fast_layer.hip: 36 B more read per trajectory and phase); there is no generic-kernel or f64 form, and the
+ * tube step and the receding driver take no weights array.  Added beside ABI 8. */
+
+/* 1 exactly where dtmpc_scenes_supported is 1 (the forward kernels' configurations); else 0.  Host-only. */
+int32_t dtmpc_weights_supported(int dtype, const dtmpc_spec* spec, const dtmpc_ilqr_cfg* cfg);
+
+/* dtmpc_ilqr_solve_scenes with per-trajectory weights; scenes may be NULL (the spec's table and the cost's target for
+ * every trajectory) or per trajectory as there.  weights == NULL is dtmpc_ilqr_solve_scenes.  DTMPC_ERR_BAD_ARG,
+ * before any device call, where dtmpc_weights_supported is 0 or the cost wraps the heading: never the shared
+ * weights in place of the array. */
+int dtmpc_ilqr_solve_weights(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost,
+                             const dtmpc_ilqr_cfg* cfg, int64_t B, const void* x0, const void* Xref,
+                             const void* Uref, void* X, void* U, void* K, void* kff, int32_t* iters,
+                             int32_t* status, int8_t* choices, void* costs, int32_t lanes, void* work,
+                             size_t work_bytes, const void* scenes, const void* weights, void* stream);
+
+/* Scratch bytes of dtmpc_solve_backward_weights: dtmpc_solve_backward_workspace_bytes' (geom == 0: g_x0 and g_obs
+ * both NULL) or dtmpc_solve_backward_geom_workspace_bytes' (geom != 0). */
+size_t dtmpc_solve_backward_weights_workspace_bytes(int dtype, int32_t horizon, int64_t B, int32_t geom);
+
+/* dtmpc_solve_backward / dtmpc_solve_backward_geom with per-trajectory weights: g_xref = -2 Q_i dx and g_target use
+ * trajectory i's own Q / Qf, and row j of g_w is the gradient w.r.t. row j of `weights`, column by column.  g_x0 and
+ * g_obs may both be NULL: the plain record (80 B per step) is then used, else the geom record (100 B), and
+ * work_bytes is held to dtmpc_solve_backward_weights_workspace_bytes accordingly.  weights == NULL is
+ * DTMPC_ERR_BAD_ARG; every other rule is dtmpc_solve_backward's, and support is dtmpc_solve_backward_supported's
+ * (any dbas_gamma). */
+int dtmpc_solve_backward_weights(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
+                                 const void* X, const void* U, const void* Xref, const void* Uref,
+                                 const void* scenes, const void* weights, const void* gX, const void* gU, void* g_w,
+                                 void* g_target, void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* work,
+                                 size_t work_bytes, int32_t* status, void* stream);
+
 
 /* ---- general (softplus / tanh parameterised) IFT path ------------------------------------ */
 /*

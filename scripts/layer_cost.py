@@ -12,7 +12,17 @@ loss.backward() as a user calls them (layout copies, the weights' device-to-host
 bytes the fused kernel moves by construction are printed beside the times.  `fused_geom` / `composition_geom`: the
 same pair for dtmpc_solve_backward_geom (the rows w.r.t. x0 and the obstacle circles as well) -- its composition
 also writes delta_lambda and forms the obstacle rows as tensor operations -- timed in the same alternated rounds, so
-`fused` beside it shows whether the old entry moved.  One JSON line."""
+`fused` beside it shows whether the old entry moved.  One JSON line.
+
+--weights adds the per-trajectory-weights entries to the same alternated rounds: `fused_weights` /
+`fused_geom_weights` (dtmpc_solve_backward_weights with the plain / the GEOM record) beside `fused` / `fused_geom`, and
+the forward at one lane -- `solve_scenes` (dtmpc_ilqr_solve_scenes, B copies of the paper's scene: the parent's
+kernel), `solve_weights_scenes` and `solve_weights` (dtmpc_ilqr_solve_weights with and without the scenes) and
+`solve_shared` (dtmpc_ilqr_solve_ws).  The weights are B copies of the cost's own, so every variant does bitwise the
+same work (checked here) and the difference is the kernel form's; `solve_weights_mixed` (five weight sets, factors in
+[0.5, 2], trajectory i -> set i % 5) is other work -- other iterates and exits -- and is printed for scale only.  Each
+forward call starts from the same zero warm start (the reset is inside the timed region of every variant alike).  The
+weights add 36 B read per trajectory and launch by construction."""
 import argparse
 import ctypes as C
 import json
@@ -49,6 +59,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default="")
+    ap.add_argument("--weights", action="store_true", help="also time the per-trajectory-weights entries")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     dev = torch.device("cuda", 0)
@@ -149,7 +160,63 @@ def main():
         ((r.X * gX).sum() + (r.V * gU).sum()).backward(retain_graph=True)
 
     ms = {k: [] for k in ("fused", "composition", "fused_geom", "composition_geom", "layer_forward", "layer_backward")}
+    wfn = {}
+    if a.weights:
+        import numpy as np
+
+        from diff_tube_mpc_strict_pt.core import pack_scenes, pack_weights
+
+        ic = cfg.to_c()
+        nine = torch.tensor([*cost.Q, *cost.R, *cost.Qf, cost.qb], dtype=torch.float64)
+        wu = nine.expand(B, 9)
+        wts = pack_weights(wu[:, 0:3], wu[:, 3:5], wu[:, 5:8], wu[:, 8], device=dev)
+        rng = np.random.default_rng(23)
+        sets = torch.cat([nine[None], nine[None] * torch.as_tensor(np.exp(rng.uniform(np.log(0.5), np.log(2.0), (4, 9))))])
+        wm = sets[torch.arange(B) % 5]
+        wts_mixed = pack_weights(wm[:, 0:3], wm[:, 3:5], wm[:, 5:8], wm[:, 8], device=dev)
+        tab64 = torch.tensor([[o.center[0], o.center[1], o.radius] for o in prob.obstacles], dtype=torch.float64)
+        sc = pack_scenes(prob, tab64.expand(B, M, 3), torch.tensor(cost.target, dtype=torch.float64).expand(B, 3),
+                         dtype=f32, device=dev)
+        gww, gtw = torch.empty(9, B, **kw), torch.empty(3, B, **kw)
+        gwgw, gtgw, gx0w, gobw = torch.empty(9, B, **kw), torch.empty(3, B, **kw), torch.empty(4, B, **kw), torch.empty(3 * M, B, **kw)
+
+        def fused_weights():
+            _lib.check(lib.dtmpc_solve_backward_weights(
+                _abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), None, None, None, wts.data_ptr(),
+                gx.data_ptr(), gu.data_ptr(), gww.data_ptr(), gtw.data_ptr(), None, None, None, None, work.data_ptr(), wb,
+                status.data_ptr(), stream), "dtmpc_solve_backward_weights")
+
+        def fused_geom_weights():
+            _lib.check(lib.dtmpc_solve_backward_weights(
+                _abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), None, None, None, wts.data_ptr(),
+                gx.data_ptr(), gu.data_ptr(), gwgw.data_ptr(), gtgw.data_ptr(), None, None, gx0w.data_ptr(),
+                gobw.data_ptr(), workg.data_ptr(), wbg, status.data_ptr(), stream), "dtmpc_solve_backward_weights")
+
+        x0s = x0.t().contiguous()
+        fX, fU = torch.empty(N + 1, 4, B, **kw), torch.empty(N, 2, B, **kw)
+        fK, fk = torch.empty(N, 8, B, **kw), torch.empty(N, 2, B, **kw)
+        fit, fst = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
+        fwb = lib.dtmpc_ilqr_workspace_bytes(_abi.F32, N, B, 1)
+        fwork = torch.empty(fwb, dtype=torch.uint8, device=dev)
+
+        def solve(scenes, weights):
+            def run():
+                fU.zero_()
+                fst.zero_()
+                _lib.check(lib.dtmpc_ilqr_solve_weights(
+                    _abi.F32, C.byref(spec), C.byref(cc), C.byref(ic), B, x0s.data_ptr(), None, None, fX.data_ptr(),
+                    fU.data_ptr(), fK.data_ptr(), fk.data_ptr(), fit.data_ptr(), fst.data_ptr(), None, None, 1,
+                    fwork.data_ptr(), fwb, None if scenes is None else scenes.data_ptr(),
+                    None if weights is None else weights.data_ptr(), stream), "dtmpc_ilqr_solve_weights")
+            return run
+
+        wfn = {"fused_weights": fused_weights, "fused_geom_weights": fused_geom_weights,
+               "solve_shared": solve(None, None), "solve_scenes": solve(sc, None), "solve_weights": solve(None, wts),
+               "solve_weights_scenes": solve(sc, wts), "solve_weights_mixed": solve(None, wts_mixed)}
+        ms.update({k: [] for k in wfn})
     for _ in range(a.rounds):
+        for k, fn in wfn.items():
+            ms[k].append(timed(fn, a.reps))
         ms["fused"].append(timed(fused, a.reps))
         ms["composition"].append(timed(composition, a.reps))
         ms["fused_geom"].append(timed(fused_geom, a.reps))
@@ -181,12 +248,37 @@ def main():
            "geom_bytes_per_launch_by_construction": (per_step + 40) * N * B + (16 + 16 + 48 + 16 + 12 * M + 4) * B,
            "geom_flagged": int((~okg).sum()), "geom_fused_vs_composition_max_rel": errg,
            "geom_old_rows_bitwise": same_old_rows}
+    if a.weights:
+        fused_weights()
+        fused_geom_weights()
+        outs = {}
+        for k in ("solve_shared", "solve_scenes", "solve_weights", "solve_weights_scenes", "solve_weights_mixed"):
+            wfn[k]()
+            torch.cuda.synchronize()
+            outs[k] = (fX.clone(), fU.clone(), fit.clone(), fst.clone())
+        same = lambda p, q: all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(p, q))  # noqa: E731
+        rec["weights"] = {
+            "bytes_added_per_traj_and_launch_by_construction": 36,
+            "backward_uniform_rows_bitwise_shared": bool(same((gw, gt), (gww, gtw))),
+            "backward_geom_uniform_rows_bitwise_shared": bool(same((gwg, gtg, gx0, gob), (gwgw, gtgw, gx0w, gobw))),
+            "forward_uniform_bitwise_shared": bool(same(outs["solve_shared"], outs["solve_weights"]) and
+                                                   same(outs["solve_scenes"], outs["solve_weights_scenes"]) and
+                                                   same(outs["solve_shared"], outs["solve_scenes"])),
+            "forward_mean_iters": {k: round(float(v[2].float().mean()), 3) for k, v in outs.items()},
+            "forward_status_nonzero": {k: int((v[3] != 0).sum()) for k, v in outs.items()}}
     for n, v in ms.items():
         rec[n] = {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
                   "spread": round(max(v) - min(v), 4)}
     rec["fused_GBps_by_construction"] = round(rec["bytes_per_launch_by_construction"] / rec["fused"]["ms_median"] / 1e6, 1)
     rec["fused_geom_GBps_by_construction"] = round(rec["geom_bytes_per_launch_by_construction"] /
                                                    rec["fused_geom"]["ms_median"] / 1e6, 1)
+    if a.weights:
+        med = lambda k: rec[k]["ms_median"]  # noqa: E731
+        rec["weights"]["ratio_of_medians"] = {
+            "solve_weights_scenes / solve_scenes": round(med("solve_weights_scenes") / med("solve_scenes"), 4),
+            "solve_weights / solve_shared": round(med("solve_weights") / med("solve_shared"), 4),
+            "fused_weights / fused": round(med("fused_weights") / med("fused"), 4),
+            "fused_geom_weights / fused_geom": round(med("fused_geom_weights") / med("fused_geom"), 4)}
     line = json.dumps(rec)
     print(line, flush=True)
     if a.out:
