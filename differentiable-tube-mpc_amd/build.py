@@ -5,7 +5,8 @@ csrc/dtmpc_kernels.hip (paper path + per-function entry points), csrc/dtmpc_fast
 the paper configuration), csrc/dtmpc_fast_ilqr.hip (its solver as the standalone batched iLQR), csrc/dtmpc_fast_general.hip (the
 general path's solves on it), csrc/dtmpc_fast_scenes.hip (both with per-trajectory scenes), csrc/dtmpc_fast_own.hip (the tube step with
 per-trajectory ancillary weights), csrc/dtmpc_fast_weights.hip (the standalone iLQR with per-trajectory cost weights),
-csrc/dtmpc_fast_layer.hip (the differentiable solve's backward), csrc/dtmpc_general.hip (general IFT
+csrc/dtmpc_fast_layer.hip (the differentiable solve's backward), csrc/dtmpc_fast_layer_dbas.hip (its rows w.r.t. the
+DBaS alpha / gamma: that file's text, the DBAS family), csrc/dtmpc_general.hip (general IFT
 path), csrc/dtmpc_receding.hip (receding-horizon nominal MPC driver), csrc/dtmpc_control.hip (tanh-box
 control map + cost derivatives), csrc/dtmpc_ocp.hip (tape cost of core/ocp.py), csrc/dtmpc_systems.hip
 (per-point kernels of the reference's per-function API: dynamics, h, barriers, Jacobians, clamp, cost
@@ -22,7 +23,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", f)
         for f in ("dtmpc_kernels.hip", "dtmpc_fast.hip", "dtmpc_fast_ilp.hip", "dtmpc_fast64.hip", "dtmpc_fast64_ilp.hip",
-                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_fast_weights.hip", "dtmpc_fast_layer.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
+                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_fast_weights.hip", "dtmpc_fast_layer.hip", "dtmpc_fast_layer_dbas.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
                   "dtmpc_control.hip", "dtmpc_ocp.hip", "dtmpc_systems.hip")]
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("dtmpc_device.hpp", "dtmpc_solver.hpp", "dtmpc_general.hpp",
                                                  "dtmpc_host.hpp", "dtmpc_ls_pk.hpp",
@@ -64,11 +65,13 @@ def up_to_date() -> bool:
 
 
 FAST = os.path.join(HERE, "csrc", "dtmpc_fast.hip")  # included by dtmpc_fast_ilqr.hip / dtmpc_fast_general.hip
+LAYER = os.path.join(HERE, "csrc", "dtmpc_fast_layer.hip")  # included by dtmpc_fast_layer_dbas.hip
 
 
 def _key(cmd, src) -> str:
     h = hashlib.sha256(" ".join(cmd).encode())
-    for p in [src, *DEPS, *([FAST] if os.path.basename(src).startswith("dtmpc_fast") else [])]:
+    for p in [src, *DEPS, *([FAST] if os.path.basename(src).startswith("dtmpc_fast") else []),
+              *([LAYER] if os.path.basename(src) == "dtmpc_fast_layer_dbas.hip" else [])]:
         h.update(open(p, "rb").read())
     return h.hexdigest()[:24]
 
@@ -185,8 +188,9 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # hold 3M obstacle-row sums on top: profiles/r12/layer_geom_resources.txt)
 # ... and the per-trajectory-weights iLQR unit (dtmpc_fast_weights): nine more per-lane values live through the whole
 # solve, beside the per-lane obstacle table of its kScene forms (profiles/r13/weights_resources.txt)
+# ... and its DBAS family's unit (dtmpc_fast_layer_dbas): two more sums (profiles/r14/layer_dbas_resources.txt)
 RESOURCE_CHECKED = ("dtmpc_fast64", "dtmpc_fast64_ilp", "dtmpc_fast64_ilqr", "dtmpc_fast64_general", "dtmpc_fast_layer",
-                    "dtmpc_fast_weights")
+                    "dtmpc_fast_layer_dbas", "dtmpc_fast_weights")
 
 
 def kernel_resources(obj: str) -> dict:

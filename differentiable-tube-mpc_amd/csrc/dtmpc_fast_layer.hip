@@ -24,6 +24,20 @@
 // tilde V_x per step as well (25 values, 100 B), forms lam_k in the forward sweep and accumulates 3M sums (geom_row).
 // WTS variant (dtmpc_solve_backward_weights, solve_backward_weights_kernel<M, TRACK, GEOM>): the nine cost weights per
 // trajectory, from a weights array [9][B] (36 B more read per trajectory); one kernel family for both record forms.
+// DBAS variant (dtmpc_solve_backward_dbas, solve_backward_dbas_kernel<M, TRACK, W>): the rows w.r.t. the barrier-state
+// parameters alpha_eff = max(alpha, eps) and gamma, the last of ift_gradient's terms that involve delta_lambda and
+// h_offset == 0 admits.  Only the barrier row b' = B(h(x')) - gamma (B(h(x)) - b) of f_hat depends on them:
+//   g_alpha_eff = sum_{m=0..N} co_m dBa(h(x_m)),  co_m = [m >= 1] lam_m - gamma [m <= N-1] lam_{m+1},
+//                 dBa(z) = dB/da = 0 for z >= a, -3 (z - a)^2 / a^4 below
+//   g_gamma     = -sum_{k<N} lam_{k+1} (B(h(x_k)) - b_k)
+// (oracle/oracle_general.h ift1's ga / gg without the softplus / tanh chain, evaluated at the tape rows).  The family
+// always has the GEOM record (25 values, no new workspace); W is the per-trajectory-weights flag.  The forward sweep
+// already holds co_k, lam_{k+1}, b_k and, inside geom_row, h(x_k): B and dBa are formed from that one evaluation and
+// two more per-lane sums are kept.  On a tape whose b_0 is the barrier of its own position B(h(x_k)) - b_k = 0 for
+// every k, whatever gamma is: the gamma row is then zero in exact arithmetic (rounding noise in f32); it is non-zero
+// only when the solve starts from a barrier state that is not the barrier of its position (a disturbed plant state,
+// the second of two chained solves).  The family is a translation unit of its own, csrc/dtmpc_fast_layer_dbas.hip
+// (this file included with DTMPC_FAST_LAYER_DBAS_TU: its 32 kernels compile beside this unit's 64, not after them).
 // All kernels include one body text, dtmpc_fast_layer_body.hpp.
 #define DTMPC_FAST_LAYER_TU 1
 #include "dtmpc_fast.hip"
@@ -77,8 +91,9 @@ struct LKG {
 // -2 (py - cy_j), -1), w_j = softmax_j(-beta h_j).  The weights and h are h_grad<M>'s (dtmpc_fast.hip) operation for
 // operation -- the same differences, exp2 arguments, sum order and reciprocal, so B' is evaluated at bitwise the h that
 // jac's linearisation saw -- with the terms kept apart instead of summed into grad h.
+// Returns h(x), the smooth-min the row was evaluated at (the DBAS variant forms B and dB/da from it).
 template <int M>
-__device__ __forceinline__ void geom_row(const FP& p, real px, real py, real co, real (&acc)[3 * M]) {
+__device__ __forceinline__ real geom_row(const FP& p, real px, real py, real co, real (&acc)[3 * M]) {
 #pragma clang fp contract(off)
   real hh[M], dxs[M], dys[M], zmax = 0.f;
 #pragma unroll
@@ -109,16 +124,20 @@ __device__ __forceinline__ void geom_row(const FP& p, real px, real py, real co,
     acc[M + i] += cw * (-2.f * dys[i]);
     acc[2 * M + i] -= cw;
   }
+  return hv;
 }
 
 template <int M, bool TRACK>
 __global__ void __launch_bounds__(kBlock) solve_backward_kernel(LK kk) {
   constexpr bool GEOM = false;
   constexpr bool WTS = false;
+  constexpr bool DBAS = false;
   real* const gx0 = nullptr;
   real* const gob = nullptr;
   const real* const wts = nullptr;
+  real* const gdb = nullptr;
   (void)wts;
+  (void)gdb;
 #include "dtmpc_fast_layer_body.hpp"
 }
 // ... and with the rows w.r.t. the start state and the obstacle circles (dtmpc_solve_backward_geom)
@@ -126,11 +145,14 @@ template <int M, bool TRACK>
 __global__ void __launch_bounds__(kBlock) solve_backward_geom_kernel(LKG kg) {
   constexpr bool GEOM = true;
   constexpr bool WTS = false;
+  constexpr bool DBAS = false;
   const LK& kk = kg.k;
   real* const gx0 = kg.gx0;
   real* const gob = kg.gob;
   const real* const wts = nullptr;
+  real* const gdb = nullptr;
   (void)wts;
+  (void)gdb;
 #include "dtmpc_fast_layer_body.hpp"
 }
 // ... and with per-trajectory cost weights (dtmpc_solve_backward_weights): both record forms, G the GEOM one
@@ -142,10 +164,32 @@ template <int M, bool TRACK, bool G>
 __global__ void __launch_bounds__(kBlock) solve_backward_weights_kernel(LKW kw) {
   constexpr bool GEOM = G;
   constexpr bool WTS = true;
+  constexpr bool DBAS = false;
   const LK& kk = kw.g.k;
   real* const gx0 = kw.g.gx0;
   real* const gob = kw.g.gob;
   const real* const wts = kw.wts;
+  real* const gdb = nullptr;
+  (void)gdb;
+#include "dtmpc_fast_layer_body.hpp"
+}
+// ... and with the rows w.r.t. the DBaS parameters (dtmpc_solve_backward_dbas): always the GEOM record, W the
+// per-trajectory-weights flag (kd.w.wts is NULL without it); g_x0 / g_obs stay optional
+struct LKD {
+  LKW w;      // p first
+  real* gdb;  // [2][B]: rows alpha_eff, gamma
+};
+template <int M, bool TRACK, bool PW>  // PW: per-trajectory weights (the body text names the workspace W)
+__global__ void __launch_bounds__(kBlock) solve_backward_dbas_kernel(LKD kd) {
+  constexpr bool GEOM = true;
+  constexpr bool WTS = PW;
+  constexpr bool DBAS = true;
+  const LK& kk = kd.w.g.k;
+  real* const gx0 = kd.w.g.gx0;
+  real* const gob = kd.w.g.gob;
+  const real* const wts = kd.w.wts;
+  real* const gdb = kd.gdb;
+  (void)wts;
 #include "dtmpc_fast_layer_body.hpp"
 }
 
@@ -168,12 +212,15 @@ static size_t layer_workspace_bytes(int32_t N, int64_t B, bool geom = false) {
   return (size_t)N * (geom ? fk::kGeomRec : fk::kLayerRec) * sizeof(real) * (size_t)B;
 }
 
-// geom: solve_backward_geom_kernel with the two further outputs (either may be NULL), else solve_backward_kernel
+// geom: solve_backward_geom_kernel with the two further outputs (either may be NULL), else solve_backward_kernel;
+// gdb (the DBAS unit only): solve_backward_dbas_kernel, wts may then be NULL
 static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int64_t B, const fk::LArgs& a,
                                  hipStream_t st, bool geom = false, real* gx0 = nullptr, real* gob = nullptr,
-                                 const real* wts = nullptr) {
-  fk::LKW kw;
-  std::memset(&kw, 0, sizeof(kw));
+                                 const real* wts = nullptr, real* gdb = nullptr) {
+  fk::LKD kd;
+  std::memset(&kd, 0, sizeof(kd));
+  fk::LKW& kw = kd.w;
+  kd.gdb = gdb;
   fk::LKG& kg = kw.g;
   fk::LK& kk = kg.k;
   kw.wts = wts;
@@ -196,6 +243,20 @@ static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int
 #else
 #define LY_CASES LY_CASE(1) LY_CASE(2) LY_CASE(3) LY_CASE(4) LY_CASE(5) LY_CASE(6) LY_CASE(7) LY_CASE(8)
 #endif
+#ifdef DTMPC_FAST_LAYER_DBAS_TU  // this unit holds the DBAS family alone
+  if (!geom || !gdb) return set_err(DTMPC_ERR_BAD_ARG, "solve backward dbas: the GEOM record and g_dbas are required");
+#define LY_LAUNCH(m, t)                                                                               \
+  do {                                                                                                \
+    if (wts) hipLaunchKernelGGL((fk::solve_backward_dbas_kernel<m, t, true>), grid, dim3(bs), 0, st, kd); \
+    else hipLaunchKernelGGL((fk::solve_backward_dbas_kernel<m, t, false>), grid, dim3(bs), 0, st, kd);    \
+  } while (0)
+  switch (sp->n_obstacles) {
+    LY_CASES
+    default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
+  }
+#undef LY_LAUNCH
+#else
+  (void)kd;
   if (wts) {  // per-trajectory weights: one family for both record forms
 #define LY_LAUNCH(m, t)                                                                                       \
   do {                                                                                                        \
@@ -222,17 +283,21 @@ static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int
     }
 #undef LY_LAUNCH
   }
+#endif
 #undef LY_CASES
 #undef LY_CASE
-  return check_launch(wts ? "solve_backward_weights_kernel" : geom ? "solve_backward_geom_kernel" : "solve_backward_kernel");
+  return check_launch(gdb ? "solve_backward_dbas_kernel" : wts ? "solve_backward_weights_kernel"
+                      : geom ? "solve_backward_geom_kernel" : "solve_backward_kernel");
 }
 
 // dtmpc_solve_backward and dtmpc_solve_backward_geom: the argument rules of include/dtmpc.h, then the launch
+// (dbas: dtmpc_solve_backward_dbas -- the GEOM record, g_dbas required, g_x0 / g_obs / weights each optional)
 static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
                                 const void* X, const void* U, const void* Xref, const void* Uref, const void* scenes,
                                 const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
                                 void* g_x0, void* g_obs, void* work, size_t work_bytes, int32_t* status,
-                                void* stream, bool wts = false, const void* weights = nullptr) {
+                                void* stream, bool wts = false, const void* weights = nullptr, bool dbas = false,
+                                void* g_dbas = nullptr) {
   if (!spec || !cost) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL spec or cost");
   if (B < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: batch must be >= 1");
   if (spec->horizon < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: horizon must be >= 1");
@@ -243,7 +308,8 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
   if (!X || !U || !gX || !gU || !g_w || !status)
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL X, U, gX, gU, g_w or status");
   if (wts && !weights) return set_err(DTMPC_ERR_BAD_ARG, "solve backward weights: NULL weights");
-  if (geom && !wts && !g_x0 && !g_obs)
+  if (dbas && !g_dbas) return set_err(DTMPC_ERR_BAD_ARG, "solve backward dbas: NULL g_dbas");
+  if (geom && !wts && !dbas && !g_x0 && !g_obs)
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward geom: g_x0 and g_obs both NULL (that is dtmpc_solve_backward)");
   if (cost->kind == DTMPC_COST_TRACK) {
     if (!Xref || !Uref) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: the tracking cost needs Xref and Uref");
@@ -252,7 +318,9 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward: Xref, Uref, g_xref and g_uref go with the tracking cost");
   }
   if (!work || work_bytes < layer_workspace_bytes(spec->horizon, B, geom))
-    return set_err(DTMPC_ERR_BAD_ARG, wts  ? "solve backward weights: work_bytes < "
+    return set_err(DTMPC_ERR_BAD_ARG, dbas ? "solve backward dbas: work_bytes < "
+                                             "dtmpc_solve_backward_dbas_workspace_bytes(...)"
+                                      : wts  ? "solve backward weights: work_bytes < "
                                              "dtmpc_solve_backward_weights_workspace_bytes(...)"
                                       : geom ? "solve backward geom: work_bytes < "
                                              "dtmpc_solve_backward_geom_workspace_bytes(...)"
@@ -273,12 +341,32 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
   a.work = (real*)work;
   a.status = status;
   return launch_solve_backward(spec, cost, B, a, (hipStream_t)stream, geom, (real*)g_x0, (real*)g_obs,
-                               (const real*)weights);
+                               (const real*)weights, (real*)g_dbas);
 }
 
 }  // namespace dtmpc
 
 extern "C" {
+
+#ifdef DTMPC_FAST_LAYER_DBAS_TU
+
+size_t dtmpc_solve_backward_dbas_workspace_bytes(int dtype, int32_t horizon, int64_t B) {
+  if (dtype != DTMPC_F32 || horizon < 1 || B < 1) return 0;
+  return dtmpc::layer_workspace_bytes(horizon, B, true);
+}
+
+int dtmpc_solve_backward_dbas(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B, const void* X,
+                              const void* U, const void* Xref, const void* Uref, const void* scenes,
+                              const void* weights, const void* gX, const void* gU, void* g_w, void* g_target,
+                              void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* g_dbas, void* work,
+                              size_t work_bytes, int32_t* status, void* stream) {
+  // always the GEOM record; weights == NULL is the shared cost
+  return dtmpc::solve_backward_entry(true, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, g_x0, g_obs, work, work_bytes, status, stream, weights != nullptr, weights,
+                                     true, g_dbas);
+}
+
+#else
 
 int32_t dtmpc_solve_backward_supported(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost) {
   return dtmpc::layer_unsupported(dtype, spec, cost) ? 0 : 1;
@@ -324,5 +412,7 @@ int dtmpc_solve_backward_weights(int dtype, const dtmpc_spec* spec, const dtmpc_
   return dtmpc::solve_backward_entry(g_x0 || g_obs, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target,
                                      g_xref, g_uref, g_x0, g_obs, work, work_bytes, status, stream, true, weights);
 }
+
+#endif  // DTMPC_FAST_LAYER_DBAS_TU
 
 }  // extern "C"

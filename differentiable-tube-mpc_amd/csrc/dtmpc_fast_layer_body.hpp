@@ -6,7 +6,14 @@
 // WTS (solve_backward_weights_kernel, dtmpc_solve_backward_weights): a third constexpr bool beside GEOM, with the
 // pointer `wts` -- the nine cost weights come from the lane's own column of the weights array [9][B] (wts_c) instead of
 // kk.c, so g_xref = -2 Q_i dx and g_target use trajectory i's own Q / Qf; with WTS false the statement is discarded.
-// No include guard: it is included three times on purpose.
+// DBAS (solve_backward_dbas_kernel, dtmpc_solve_backward_dbas): a fourth constexpr bool, valid with GEOM only, with the
+// pointer `gdb` [2][B] -- the rows w.r.t. alpha_eff = max(alpha, eps) and gamma: from geom_row's one evaluation of
+// h(x_m) the forward sweep also forms dBa(h) = -3 (h - a)^2 / a^4 below a (0 at and above it) and B(h) (vbarrier) and
+// keeps the sums g_alpha_eff += co_m dBa, g_gamma -= lam_{k+1} (B(h(x_k)) - b_k); row N adds its alpha term only.
+// With b_0 = B(h(x_0)) every B(h(x_k)) - b_k is zero on a rolled-out tape and the gamma row is rounding noise.  With
+// DBAS false every `if constexpr (DBAS)` statement is discarded.
+// No include guard: it is included four times on purpose.
+  static_assert(GEOM || !DBAS, "DBAS needs the GEOM record");
   constexpr int REC = GEOM ? kGeomRec : kLayerRec;
   using LFwd = typename std::conditional<GEOM && (M > 0), LFwdInG, LFwdIn>::type;  // (M > 0: a dependent type)
   const LArgs& a = kk.a;
@@ -179,6 +186,12 @@
   (void)go;
   (void)lam;
   (void)lamN;
+  // DBAS: the two sums g_alpha_eff, g_gamma; dBa(z) = dba_c (z - a)^2 below a, dba_c = -3 / a^4
+  real ga = 0.f, gg = 0.f, dba_c = 0.f;
+  if constexpr (DBAS) dba_c = -3.f / (p.a2 * p.a2);
+  (void)ga;
+  (void)gg;
+  (void)dba_c;
   bool ok = true;
   if constexpr (GEOM) ok = ok0;
   LFwd Fn;
@@ -223,7 +236,17 @@
       // then tape row k's coefficient c_k / B'(h(x_k)) = [k >= 1] lam_k - gamma lam_{k+1}
       const real ln = k + 1 < N ? Fn.L[4] + (Fn.L[0] * n0 + Fn.L[1] * n1 + Fn.L[2] * n2 + Fn.L[3] * n3)
                                 : lamN + pxx[3] * n3;
-      geom_row<M>(p, F.x[0], F.x[1], lam - g * ln, go);
+      if constexpr (DBAS) {
+        // the same evaluation of h(x_k): co_k dBa(h) into the alpha sum, -lam_{k+1} (B(h) - b_k) into the gamma sum
+        const real co = lam - g * ln;
+        const real hv = geom_row<M>(p, F.x[0], F.x[1], co, go);
+        const real df = hv - p.a;
+        const real ta = co * (dba_c * (df * df));
+        ga += hv >= p.a ? 0.f : ta;
+        gg -= ln * (vbarrier(p, hv) - F.x[3]);
+      } else {
+        geom_row<M>(p, F.x[0], F.x[1], lam - g * ln, go);
+      }
       lam = ln;
     }
     d[0] = n0;
@@ -232,7 +255,17 @@
     d[3] = n3;
   }
   if constexpr (GEOM) {  // row N: c_N = B'(h(x_N)) lam_N
-    geom_row<M>(p, X[(size_t)(4 * N) * nb], X[(size_t)(4 * N + 1) * nb], lam, go);
+    if constexpr (DBAS) {  // row N adds its alpha term only (co_N = lam_N; no step leaves x_N)
+      const real hv = geom_row<M>(p, X[(size_t)(4 * N) * nb], X[(size_t)(4 * N + 1) * nb], lam, go);
+      const real df = hv - p.a;
+      const real ta = lam * (dba_c * (df * df));
+      ga += hv >= p.a ? 0.f : ta;
+      gdb[i] = ga;
+      gdb[nb + i] = gg;
+      ok = ok && finite(ga) && finite(gg);
+    } else {
+      geom_row<M>(p, X[(size_t)(4 * N) * nb], X[(size_t)(4 * N + 1) * nb], lam, go);
+    }
     real* GO = gob ? gob + i : nullptr;
 #pragma unroll
     for (int j = 0; j < 3 * M; ++j) {

@@ -268,6 +268,13 @@ PROTOTYPES = {
         [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
          C.c_size_t, P, P],
     ),
+    # the rows w.r.t. the DBaS alpha / gamma (beside ABI 8): dtmpc_solve_backward_weights' arguments, g_dbas after g_obs
+    "dtmpc_solve_backward_dbas_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64]),
+    "dtmpc_solve_backward_dbas": (
+        C.c_int,
+        [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+         C.c_size_t, P, P],
+    ),
     "dtmpc_sensitivity_upper_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64]),
     "dtmpc_ddp_sensitivity_upper": (
         C.c_int,

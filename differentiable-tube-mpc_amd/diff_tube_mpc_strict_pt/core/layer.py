@@ -15,12 +15,24 @@ delta_lambda,
     c_m = B'(h(x_m)) ([m >= 1] lam_m - gamma [m <= N-1] lam_{m+1}),  lam_k = dlam_k[3]          m = 0 .. N
     g_cx_j = sum_m c_m w_j(x_m) (-2 (px_m - cx_j)),  g_cy_j alike,  g_r_j = 2 r_j sum_m c_m w_j(x_m) (-1)
 with w_j = softmax_j(-beta h_j) (only the barrier row of f_hat sees the obstacles).  b_0's own dependence on the
-position and the scene is the caller's to express (``dbas_init_b0`` is differentiable).  Gradients w.r.t. the warm
-start and the DBaS parameters (alpha, gamma, tightening) are not provided; the last remain ``ift_gradient``'s.
+position and the scene is the caller's to express (``dbas_init_b0`` is differentiable).
+
+On request (``want_dbas``; ``dbas_alpha=`` / ``dbas_gamma=`` of the layer) also the rows w.r.t. the barrier-state
+parameters alpha and gamma, the remaining delta_lambda terms: with co_m = [m >= 1] lam_m - gamma [m <= N-1] lam_{m+1}
+and a = max(alpha, eps),
+    g_alpha = dmax sum_{m=0..N} co_m dBa(h(x_m)),   dBa(z) = 0 for z >= a, -3 (z - a)^2 / a^4 below
+    g_gamma = -sum_{k=0..N-1} lam_{k+1} (B(h(x_k)) - b_k)
+with dmax = d max(alpha, eps) / d alpha = 1 (alpha > eps), 0.5 (alpha == eps), 0 (alpha < eps), applied on the host
+(``ift_gradient``'s alpha / gamma columns without the softplus / tanh chain, h evaluated at the tape rows, which a
+rolled-out tape makes x' = f(x_k, u_k) to rounding).  If b_0 = B(h(x_0)) then B(h(x_k)) - b_k = 0 for every k
+whatever gamma is: the gamma row is then zero in exact arithmetic (rounding noise in f32).  It is non-zero only when
+the solve starts from a barrier state that is not the barrier of its position: a plant state after a disturbance, the
+second of two chained solves.  Gradients w.r.t. the warm start, the tightening, dbas_eps and obs_beta are not
+provided; the tightening's remains ``ift_gradient``'s.
 
 Where ``dtmpc_solve_backward_supported`` says yes (f32, smooth-min, 1..8 obstacles, relaxed inverse barrier) the
 rows come from ONE launch of the fused kernel (csrc/dtmpc_fast_layer.hip; dtmpc_solve_backward_geom when x0 or
-obstacle rows are wanted), which writes no sensitivity tape;
+obstacle rows are wanted, dtmpc_solve_backward_dbas when the DBaS rows are), which writes no sensitivity tape;
 elsewhere (f64, min / single aggregation, log barrier) from ``dtmpc_ddp_sensitivity_upper`` and a few tensor
 operations."""
 from __future__ import annotations
@@ -51,6 +63,7 @@ class SolveGradient:
     X_ref: Optional[Tensor]    # [B, N+1, 3] (tracking cost)
     U_ref: Optional[Tensor]    # [B, N, 2]
     status: Tensor             # [B] int32, DTMPC_ST_NONFINITE where a row is not finite
+    dbas: Optional[Tensor] = None       # [B, 2]: the DBaS alpha, gamma (want_dbas)
     x0: Optional[Tensor] = None         # [B, 4] (want_x0)
     obstacles: Optional[Tensor] = None  # [B, M, 3]: (cx, cy, r) of each circle (want_obstacles)
 
@@ -84,10 +97,46 @@ def _obstacle_rows(problem: DubinsDBaSProblem, X: Tensor, dlam: Tensor) -> Tenso
     return torch.stack([(cw * (-2.0 * dx)).sum(1), (cw * (-2.0 * dy)).sum(1), -cw.sum(1) * (2.0 * tab[:, 2])], 2)
 
 
+def _dbas_dmax(problem: DubinsDBaSProblem) -> float:
+    """d max(alpha, eps) / d alpha: the factor between the alpha_eff row and the alpha row."""
+    a, e = float(problem.dbas_alpha), float(problem.dbas_eps)
+    return 1.0 if a > e else (0.5 if a == e else 0.0)
+
+
+def _dbas_host(problem: DubinsDBaSProblem, gdb: Tensor) -> Tensor:
+    """[2, B] (alpha_eff, gamma) -> [B, 2] (alpha, gamma): the dmax factor on the alpha row (exact zeros at 0)."""
+    d = _dbas_dmax(problem)
+    ga = gdb[0] * d if d != 0.0 else torch.zeros_like(gdb[0])
+    return torch.stack([ga, gdb[1]], 1)
+
+
+def _dbas_rows(problem: DubinsDBaSProblem, X: Tensor, dlam: Tensor) -> Tensor:
+    """The DBaS rows [B, 2] (alpha_eff, gamma) from a sensitivity's delta_lambda [B, N+1, 4] as tensor operations (the
+    module docstring's formulas; smooth-min and the relaxed inverse barrier, the problem's shared circles)."""
+    kw = dict(dtype=X.dtype, device=X.device)
+    N = X.shape[1] - 1
+    tab = torch.tensor([[o.center[0], o.center[1], o.radius] for o in problem.obstacles], **kw)
+    dx = X[..., 0:1] - tab[:, 0]  # [B, N+1, M]
+    dy = X[..., 1:2] - tab[:, 1]
+    z = -float(problem.obs_beta) * (dx * dx + dy * dy - tab[:, 2] * tab[:, 2])
+    h = -torch.logsumexp(z, -1) / float(problem.obs_beta)
+    Bv = barrier_and_derivative(h, kind=_abi.BARRIER_INVERSE, alpha=float(problem.dbas_alpha),
+                                eps=float(problem.dbas_eps), want_B=True, want_dB=False)[0]
+    a = max(float(problem.dbas_alpha), float(problem.dbas_eps))
+    dBa = torch.where(h >= a, torch.zeros_like(h), -3.0 * (h - a) ** 2 / a ** 4)
+    lam = dlam[..., 3]
+    zero = torch.zeros_like(lam[:, :1])
+    co = torch.cat([zero, lam[:, 1:]], 1) - float(problem.dbas_gamma) * torch.cat([lam[:, 1:], zero], 1)
+    ga = (co * dBa).sum(1)
+    gg = -(lam[:, 1:] * (Bv[:, :N] - X[:, :N, 3])).sum(1)
+    return torch.stack([ga, gg], 1)
+
+
 def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor, V: Tensor, grad_X: Tensor,
                    grad_V: Tensor, X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
                    scenes: Optional[Tensor] = None, check: bool = True, want_x0: bool = False,
-                   want_obstacles: bool = False, weights: Optional[Tensor] = None) -> SolveGradient:
+                   want_obstacles: bool = False, weights: Optional[Tensor] = None,
+                   want_dbas: bool = False) -> SolveGradient:
     """The gradient of an upper loss w.r.t. the plain cost weights and the references, per trajectory, from the
     loss's gradients ``grad_X`` [B, N+1, 4] / ``grad_V`` [B, N, 2] w.r.t. the tape (X [B, N+1, 4], V [B, N, 2]).
 
@@ -108,7 +157,14 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
     weights ([9, B] float32, pack_weights): trajectory i is differentiated with its own Q, R, Qf, qb (``cost``'s nine
     weights are then unused), so ``X_ref`` / ``target`` rows carry its own Q / Qf and row i of ``weights`` in the
     result is the gradient w.r.t. column i of the array.  Fused f32 kernel only (dtmpc_solve_backward_weights, any
-    dbas_gamma): the composition paths (f64, min / single aggregation, the log barrier) raise ValueError."""
+    dbas_gamma): the composition paths (f64, min / single aggregation, the log barrier) raise ValueError.
+
+    want_dbas: also the rows w.r.t. the barrier-state parameters (``dbas`` [B, 2]: alpha, gamma; the module docstring's
+    formulas, the alpha row with d max(alpha, eps) / d alpha applied).  The fused kernel (dtmpc_solve_backward_dbas:
+    composes with scenes, weights, want_x0 and want_obstacles in the one launch) or, on f64, the composition without
+    scenes; like the obstacle rows they need smooth-min aggregation and the relaxed inverse barrier, else ValueError.
+    On a tape whose b_0 is the barrier of its own start position the gamma row is zero up to rounding (see the module
+    docstring): it carries information only for a solve started from a disturbed or chained barrier state."""
     if cost.wrap_angle:
         raise ValueError("solve_backward: a cost with wrap_angle is not supported (the reference's sensitivity "
                          "closures carry no wrapped heading error)")
@@ -144,7 +200,10 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         gur = torch.empty(N, 2, B, **kw) if track else None
         gx0 = torch.empty(4, B, **kw) if want_x0 else None
         gob = torch.empty(3, M, B, **kw) if want_obstacles else None
-        if weights is not None:
+        gdb = torch.empty(2, B, **kw) if want_dbas else None
+        if want_dbas:
+            wb = int(lib.dtmpc_solve_backward_dbas_workspace_bytes(_dtype_code(X), N, B))
+        elif weights is not None:
             wb = int(lib.dtmpc_solve_backward_weights_workspace_bytes(_dtype_code(X), N, B, 1 if geom else 0))
         else:
             nbytes = (lib.dtmpc_solve_backward_geom_workspace_bytes if geom
@@ -155,7 +214,10 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         head = (_dtype_code(X), C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), _ptr(Xr), _ptr(Ur),
                 _ptr(scenes), gx.data_ptr(), gu.data_ptr(), gw.data_ptr(), _ptr(gt), _ptr(gxr), _ptr(gur))
         tail = (work.data_ptr(), wb, status.data_ptr(), _lib.stream_of(X))
-        if weights is not None:  # the WTS family: the plain record, or the GEOM one when x0 / obstacle rows are wanted
+        if want_dbas:  # the DBAS family: the GEOM record, weights / x0 / obstacle rows as asked for
+            _lib.check(lib.dtmpc_solve_backward_dbas(*head[:9], _ptr(weights), *head[9:], _ptr(gx0), _ptr(gob),
+                                                     gdb.data_ptr(), *tail), "dtmpc_solve_backward_dbas")
+        elif weights is not None:  # the WTS family: the plain record, or the GEOM one when x0 / obstacle rows are wanted
             _lib.check(lib.dtmpc_solve_backward_weights(*head[:9], weights.data_ptr(), *head[9:], _ptr(gx0), _ptr(gob),
                                                         *tail), "dtmpc_solve_backward_weights")
         elif geom:  # the GEOM variant of the kernel: the same rows, and those w.r.t. x0 / (cx, cy, r^2)
@@ -171,7 +233,8 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
             rows = torch.stack([gob[0], gob[1], gob[2] * (2.0 * r)], 2).permute(1, 0, 2).contiguous()
         out = SolveGradient(weights=gw.t().contiguous(), target=None if track else gt.t().contiguous(),
                             X_ref=from_soa(gxr) if track else None, U_ref=from_soa(gur) if track else None,
-                            status=status, x0=gx0.t().contiguous() if want_x0 else None, obstacles=rows)
+                            status=status, x0=gx0.t().contiguous() if want_x0 else None, obstacles=rows,
+                            dbas=_dbas_host(problem, gdb) if want_dbas else None)
     else:
         if weights is not None:
             raise ValueError("solve_backward: per-trajectory weights need the fused kernel "
@@ -185,7 +248,10 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
             raise ValueError("solve_backward: obstacle rows need smooth-min aggregation and the relaxed inverse "
                              "barrier (min / single aggregation have no softmax weights; the log barrier's rows "
                              "are not provided)")
-        s = _ddp_sensitivity_upper(problem, cost, X, V, grad_X, grad_V, geom, False)
+        if want_dbas and (problem.obs_aggregation != "smoothmin" or problem.barrier_type != "inverse" or M < 1):
+            raise ValueError("solve_backward: the DBaS rows need smooth-min aggregation and the relaxed inverse "
+                             "barrier (the log barrier's rows are not provided)")
+        s = _ddp_sensitivity_upper(problem, cost, X, V, grad_X, grad_V, geom or want_dbas, False)
         dX, dV = s.delta_X, s.delta_V
         Q = torch.tensor(cost.Q, **kw)
         R = torch.tensor(cost.R, **kw)
@@ -206,9 +272,11 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         gt = None if track else gxr.sum(1)
         gx0 = s.delta_lambda[:, 0].contiguous() if want_x0 else None
         gob = _obstacle_rows(problem, X, s.delta_lambda) if want_obstacles else None
-        status = _nonfinite_status(gw, gt, gxr if track else None, gur if track else None, dX[:, N], gx0, gob)
+        gdb = _dbas_rows(problem, X, s.delta_lambda) if want_dbas else None
+        status = _nonfinite_status(gw, gt, gxr if track else None, gur if track else None, dX[:, N], gx0, gob, gdb)
         out = SolveGradient(weights=gw, target=gt, X_ref=gxr if track else None, U_ref=gur if track else None,
-                            status=status, x0=gx0, obstacles=gob)
+                            status=status, x0=gx0, obstacles=gob,
+                            dbas=_dbas_host(problem, gdb.t()) if want_dbas else None)
     if check:
         raise_for_status(out.status, "solve_backward")
     return out
@@ -216,17 +284,18 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
 
 class _Solve(torch.autograd.Function):
     """X*, V* of a finished solve as functions of the weight / reference tensors (and, named in ``wrt``, of the
-    start state and the obstacle circles: x0 / obstacles are None otherwise): forward hands the tape through,
-    backward is solve_backward at that tape."""
+    start state and the obstacle circles: x0 / obstacles are None otherwise; dbas_alpha / dbas_gamma: the layer's
+    arguments of those names or None): forward hands the tape through, backward is solve_backward at that tape."""
 
     @staticmethod
     def forward(ctx, X, V, problem, cost, scenes, per_traj_target, nref, Q, R, Qf, qb, target, X_ref, U_ref,
-                x0=None, obstacles=None, weights=None):
+                x0=None, obstacles=None, weights=None, dbas_alpha=None, dbas_gamma=None):
         ctx.problem, ctx.cost, ctx.scenes = problem, cost, scenes
         ctx.weights = weights  # [9, B] packed (detached) or None: Q, R, Qf, qb are then [B, .] and get their rows
         ctx.per_traj_target, ctx.nref = per_traj_target, nref
         ctx.shapes = tuple(None if t is None else (t.shape, t.dtype)
                            for t in (Q, R, Qf, qb, target, X_ref, U_ref, x0, obstacles))
+        ctx.dbas_shapes = tuple(None if t is None else (t.shape, t.dtype) for t in (dbas_alpha, dbas_gamma))
         ctx.save_for_backward(X, V, *(t for t in (X_ref, U_ref) if t is not None))
         ctx.flagged = None
         return X.clone(), V.clone()
@@ -239,11 +308,14 @@ class _Solve(torch.autograd.Function):
         gV = torch.zeros_like(V) if gV is None else gV
         sh = ctx.shapes
         need = ctx.needs_input_grad[7:]
+        dsh = ctx.dbas_shapes
+        need_db = tuple(dsh[j] is not None and need[10 + j] for j in range(2))
         g = solve_backward(problem=ctx.problem, cost=ctx.cost, X=X, V=V, grad_X=gX.contiguous(),
                            grad_V=gV.contiguous(), X_ref=None if Xr is None else Xr.detach(),
                            U_ref=None if Ur is None else Ur.detach(), scenes=ctx.scenes, weights=ctx.weights,
                            check=False,
-                           want_x0=sh[7] is not None and need[7], want_obstacles=sh[8] is not None and need[8])
+                           want_x0=sh[7] is not None and need[7], want_obstacles=sh[8] is not None and need[8],
+                           want_dbas=any(need_db))
         keep = (g.status == 0)
         ctx.flagged = g.status  # [B] int32: the trajectories left out of this backward
 
@@ -271,7 +343,13 @@ class _Solve(torch.autograd.Function):
         if g.obstacles is not None:  # [M, 3]: the shared circles get the sum over the batch
             o = rows(g.obstacles)
             out[8] = (o.sum(0) if len(sh[8][0]) == 2 else o).to(sh[8][1])
-        return (None,) * 7 + tuple(out) + (None,)
+        gdb = [None, None]
+        if g.dbas is not None:  # one value each: the sum of the unflagged trajectories' rows
+            d = rows(g.dbas).sum(0)
+            for j in range(2):
+                if need_db[j]:
+                    gdb[j] = d[j].reshape(dsh[j][0]).to(dsh[j][1])
+        return (None,) * 7 + tuple(out) + (None,) + tuple(gdb)
 
 
 @dataclass(frozen=True)
@@ -289,7 +367,8 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
                     qb: Tensor, x0: Tensor, V_init: Tensor, target: Optional[Tensor] = None,
                     X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
                     obstacles: Optional[Tensor] = None, lanes: int = 0, check: bool = True,
-                    wrt: Sequence[str] = ()) -> ILQRResult:
+                    wrt: Sequence[str] = (), dbas_alpha: Optional[Tensor] = None,
+                    dbas_gamma: Optional[Tensor] = None) -> ILQRResult:
     """``ilqr_solve`` whose X* / V* are differentiable w.r.t. Q [3], R [2], Qf [3], qb [], the target ([3] shared
     or [B, 3] per trajectory; kind 'target') and X_ref [B, N+1, >=3] / U_ref [B, N, 2] (kind 'track').
 
@@ -318,9 +397,18 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
     shared, expanded through ``pack_scenes``) may require grad and receives its rows (the [M, 3] form their sum over
     the batch), see the module docstring.
 
+    dbas_alpha / dbas_gamma (opt-in): a zero-dim or one-element tensor each, whose VALUE replaces ``problem``'s float
+    of that name in the forward and the backward (read in the same device-to-host read as the weights) and which, if
+    it requires grad, receives the sum of the unflagged trajectories' rows of ``solve_backward(want_dbas=True)`` (the
+    module docstring's formulas; a learnable parameterisation such as softplus / tanh is the caller's, in torch).  On
+    a solve whose b_0 is the barrier of its start position the gamma gradient is zero up to rounding: it carries
+    information for a disturbed or chained start state.  A [B] tensor is refused: per-trajectory DBaS parameters
+    are not built (they would need forward kernels).  Passing neither leaves every path as it is.
+
     Refused: without ``wrt`` gradients w.r.t. x0 and obstacles; always w.r.t. V_init (the warm start is not an
-    argument of the optimum), a wrapped heading error, and DBaS parameters as tensors (their gradients remain
-    ``ift_gradient``'s).  check: the forward raises as ``ilqr_solve`` does."""
+    argument of the optimum), a wrapped heading error, ``problem.dbas_*`` / ``problem.obs_beta`` as tensors (alpha
+    and gamma go through ``dbas_alpha=`` / ``dbas_gamma=``; gradients w.r.t. dbas_eps and obs_beta are not provided).
+    check: the forward raises as ``ilqr_solve`` does."""
     if kind not in ("target", "track"):
         raise ValueError(f"unknown cost kind {kind!r}")
     if isinstance(wrt, str) or any(w not in ("x0", "obstacles") for w in wrt):
@@ -336,11 +424,24 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
                          "initial state (xi), and the warm start is not an argument of the optimum; detach them")
     if obstacles is not None and isinstance(obstacles, Tensor) and obstacles.requires_grad and not wrt_obs:
         raise ValueError("diff_ilqr_solve: no gradient w.r.t. the obstacle geometry; detach obstacles")
-    for name in ("dbas_alpha", "dbas_gamma", "dbas_eps", "obs_beta"):
+    for name in ("dbas_alpha", "dbas_gamma"):
         if isinstance(getattr(problem, name), Tensor):
-            raise ValueError(f"diff_ilqr_solve: problem.{name} must be a float -- gradients w.r.t. the DBaS "
-                             "parameters remain ift_gradient's")
+            raise ValueError(f"diff_ilqr_solve: problem.{name} must be a float -- pass the tensor as the argument "
+                             f"{name}= of diff_ilqr_solve to receive its gradient (the raw-parameter chain stays "
+                             "ift_gradient's)")
+    for name in ("dbas_eps", "obs_beta"):
+        if isinstance(getattr(problem, name), Tensor):
+            raise ValueError(f"diff_ilqr_solve: problem.{name} must be a float -- gradients w.r.t. dbas_eps and "
+                             "obs_beta are not provided")
     B, N = x0.shape[0], problem.horizon
+    dbas = tuple((name, t) for name, t in (("dbas_alpha", dbas_alpha), ("dbas_gamma", dbas_gamma)) if t is not None)
+    for name, t in dbas:
+        if not isinstance(t, Tensor):
+            raise ValueError(f"diff_ilqr_solve: {name} is a zero-dim or one-element tensor (a float goes in problem)")
+        if t.numel() != 1:
+            raise ValueError(f"diff_ilqr_solve: {name} must be a zero-dim or one-element tensor, got "
+                             f"{tuple(t.shape)} -- per-trajectory DBaS parameters are not built (they would need "
+                             "forward kernels)")
     # the weights' shapes (before anything needs a device): all four shared -- today's path -- or any per trajectory
     # (a one-element qb beside 1-D Q, R, Qf is the shared form, as it always was)
     shared_w = not (Q.dim() == 2 or R.dim() == 2 or Qf.dim() == 2 or (qb.dim() == 1 and qb.numel() != 1))
@@ -381,7 +482,11 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
     # one device-to-host read: the ABI's cost weights are host doubles
     host = torch.cat([t.detach().reshape(-1)[:k].to(torch.float64) for t, k in
                       ((Q, 3), (R, 2), (Qf, 3), (qb, 1)) + (((target, 3),) if (not track and not per_traj) else ())]
+                     + [t.detach().reshape(-1).to(device=x0.device, dtype=torch.float64) for _, t in dbas]
                      ).cpu().tolist()
+    if dbas:  # the DBaS values ride at the end of the same read
+        problem = dataclasses.replace(problem, **{name: v for (name, _), v in zip(dbas, host[-len(dbas):])})
+        host = host[:-len(dbas)]
     cost = QuadraticCost(kind=kind, Q=tuple(host[0:3]), R=tuple(host[3:5]), Qf=tuple(host[5:8]), qb=host[8],
                          target=tuple(host[9:12]) if len(host) > 9 else (0.0, 0.0, 0.0))
     scenes = None
@@ -400,7 +505,7 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
                      **({} if wts is None else {"weights": wts}))
     nref = 0 if X_ref is None else X_ref.shape[-1]
     Xd, Vd = _Solve.apply(res.X, res.V, problem, cost, scenes, per_traj, nref, Q, R, Qf, qb, target, X_ref, U_ref,
-                          x0 if wrt_x0 else None, obstacles if wrt_obs else None, wts)
+                          x0 if wrt_x0 else None, obstacles if wrt_obs else None, wts, dbas_alpha, dbas_gamma)
     fields = {f.name: getattr(res, f.name) for f in dataclasses.fields(ILQRResult)}
     fields.update(X=Xd, V=Vd)
     return DiffILQRResult(**fields, _node=Xd.grad_fn)

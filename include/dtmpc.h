@@ -449,7 +449,8 @@ int dtmpc_tube_step_own(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg*
  *   g_xref[k][i] = -2 Q_i dx_k[i] (Qf_i at k = N),  g_uref[k][j] = -2 R_j du_k[j];
  *   g_target[i] = sum_k g_xref[k][i] with r_k = target, ubar = 0.
  * It is the reference's IFT at the given tape (Gauss-Newton L_zz, active set frozen): the gradient of the solver's
- * output only where the solve has converged.  Gradients w.r.t. the DBaS parameters remain dtmpc_ift_gradient's.
+ * output only where the solve has converged.  The rows w.r.t. the DBaS alpha and gamma are
+ * dtmpc_solve_backward_dbas's (below); the tightening's remains dtmpc_ift_gradient's.
  * Added beside ABI 8 (csrc/dtmpc_fast_layer.hip); discovered through dtmpc_solve_backward_supported. */
 
 /* 1 for DTMPC_F32, smooth-min aggregation over 1..8 obstacles, the relaxed inverse barrier, h_offset == 0 and an
@@ -537,6 +538,36 @@ int dtmpc_solve_backward_weights(int dtype, const dtmpc_spec* spec, const dtmpc_
                                  const void* scenes, const void* weights, const void* gX, const void* gU, void* g_w,
                                  void* g_target, void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* work,
                                  size_t work_bytes, int32_t* status, void* stream);
+
+/* ---- differentiable solve: the rows w.r.t. the DBaS parameters alpha and gamma ------------- */
+/*
+ * The last of ift_gradient's terms that involve delta_lambda and h_offset == 0 admits (the tightening's row needs
+ * h_offset != 0).  Only the barrier row b' = B(h(x')) - gamma (B(h(x)) - b) of f_hat depends on the two parameters;
+ * with lam_k = dlam_k[3], co_m = [m >= 1] lam_m - gamma [m <= N-1] lam_{m+1} (m = 0..N) and a = max(alpha, eps),
+ *   g_dbas [2][B]:  row 0  g_alpha_eff = sum_{m=0..N} co_m dBa(h(x_m)),  dBa(z) = 0 for z >= a, -3 (z - a)^2 / a^4 below;
+ *                   row 1  g_gamma     = -sum_{k=0..N-1} lam_{k+1} (B(h(x_k)) - b_k)
+ * (dtmpc_ift_gradient's columns DTMPC_P_ALPHA / DTMPC_P_GAMMA without the softplus / tanh chain, h evaluated at the
+ * tape rows).  Row 0 is w.r.t. alpha_eff: d alpha_eff / d alpha (1 for alpha > eps, 0 below) is the caller's factor.
+ * If b_0 = B(h(x_0)) then B(h(x_k)) - b_k = 0 along a rolled-out tape whatever gamma is: row 1 is zero in exact
+ * arithmetic (rounding noise in f32) and is non-zero only for a solve that starts from a barrier state that is not
+ * the barrier of its position (a disturbed plant state, the second of two chained solves).
+ * The kernels (solve_backward_dbas_kernel, csrc/dtmpc_fast_layer_dbas.hip) are dtmpc_solve_backward_geom's with two
+ * more per-lane sums formed from the evaluation of h the obstacle rows already make: the same record (100 B per step
+ * and trajectory), no further workspace.  Added beside ABI 8; supported where dtmpc_solve_backward_supported says so. */
+
+/* Scratch bytes of dtmpc_solve_backward_dbas: dtmpc_solve_backward_geom_workspace_bytes' (0 as there). */
+size_t dtmpc_solve_backward_dbas_workspace_bytes(int dtype, int32_t horizon, int64_t B);
+
+/* dtmpc_solve_backward_weights' arguments with g_dbas [2][B] after g_obs.  weights may be NULL (the cost's own nine
+ * weights for every trajectory); g_x0 and g_obs may each be NULL (the geom record is used either way); g_dbas == NULL
+ * is DTMPC_ERR_BAD_ARG.  work_bytes is held to dtmpc_solve_backward_dbas_workspace_bytes; every other rule is
+ * dtmpc_solve_backward's, checked before any device call, and support is dtmpc_solve_backward_supported's (any
+ * dbas_gamma).  The status word also covers the two new rows. */
+int dtmpc_solve_backward_dbas(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
+                              const void* X, const void* U, const void* Xref, const void* Uref, const void* scenes,
+                              const void* weights, const void* gX, const void* gU, void* g_w, void* g_target,
+                              void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* g_dbas, void* work,
+                              size_t work_bytes, int32_t* status, void* stream);
 
 
 /* ---- general (softplus / tanh parameterised) IFT path ------------------------------------ */

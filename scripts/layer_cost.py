@@ -22,7 +22,13 @@ kernel), `solve_weights_scenes` and `solve_weights` (dtmpc_ilqr_solve_weights wi
 same work (checked here) and the difference is the kernel form's; `solve_weights_mixed` (five weight sets, factors in
 [0.5, 2], trajectory i -> set i % 5) is other work -- other iterates and exits -- and is printed for scale only.  Each
 forward call starts from the same zero warm start (the reset is inside the timed region of every variant alike).  The
-weights add 36 B read per trajectory and launch by construction."""
+weights add 36 B read per trajectory and launch by construction.
+
+--dbas adds dtmpc_solve_backward_dbas (the rows w.r.t. the DBaS alpha / gamma as well: 8 B more written per trajectory
+and launch, the same record) to the same alternated rounds, each call timed right after its twin of the same (M, kind):
+`fused_dbas` after `fused_geom` (M = 5, target cost), and for the tracking cost `fused_geom_track` / `fused_dbas_track`
+(references = the tape's own positions and controls; both entries with g_xref / g_uref, g_x0 and g_obs passed).  The
+rows both entries write are compared bitwise here."""
 import argparse
 import ctypes as C
 import json
@@ -60,6 +66,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default="")
     ap.add_argument("--weights", action="store_true", help="also time the per-trajectory-weights entries")
+    ap.add_argument("--dbas", action="store_true", help="also time dtmpc_solve_backward_dbas beside its geom twins")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     dev = torch.device("cuda", 0)
@@ -214,12 +221,51 @@ def main():
                "solve_shared": solve(None, None), "solve_scenes": solve(sc, None), "solve_weights": solve(None, wts),
                "solve_weights_scenes": solve(sc, wts), "solve_weights_mixed": solve(None, wts_mixed)}
         ms.update({k: [] for k in wfn})
+    dfn = {}
+    if a.dbas:
+        import dataclasses
+
+        gdb, gwd, gtd = torch.empty(2, B, **kw), torch.empty(9, B, **kw), torch.empty(3, B, **kw)
+        gx0d, gobd = torch.empty(4, B, **kw), torch.empty(3 * M, B, **kw)
+        ct = dataclasses.replace(cost, kind="track").to_c()
+        Xr, Ur = Xs[:, :3].contiguous(), Us.clone()
+        trk = {k: (torch.empty(9, B, **kw), torch.empty(N + 1, 3, B, **kw), torch.empty(N, 2, B, **kw),
+                   torch.empty(4, B, **kw), torch.empty(3 * M, B, **kw)) for k in ("geom", "dbas")}
+        gdbt = torch.empty(2, B, **kw)
+
+        def fused_dbas():
+            _lib.check(lib.dtmpc_solve_backward_dbas(
+                _abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), None, None, None, None,
+                gx.data_ptr(), gu.data_ptr(), gwd.data_ptr(), gtd.data_ptr(), None, None, gx0d.data_ptr(),
+                gobd.data_ptr(), gdb.data_ptr(), workg.data_ptr(), wbg, status.data_ptr(), stream),
+                "dtmpc_solve_backward_dbas")
+
+        def fused_geom_track():
+            w9, xr, ur, g0, go = trk["geom"]
+            _lib.check(lib.dtmpc_solve_backward_geom(
+                _abi.F32, C.byref(spec), C.byref(ct), B, Xs.data_ptr(), Us.data_ptr(), Xr.data_ptr(), Ur.data_ptr(), None,
+                gx.data_ptr(), gu.data_ptr(), w9.data_ptr(), None, xr.data_ptr(), ur.data_ptr(), g0.data_ptr(),
+                go.data_ptr(), workg.data_ptr(), wbg, status.data_ptr(), stream), "dtmpc_solve_backward_geom")
+
+        def fused_dbas_track():
+            w9, xr, ur, g0, go = trk["dbas"]
+            _lib.check(lib.dtmpc_solve_backward_dbas(
+                _abi.F32, C.byref(spec), C.byref(ct), B, Xs.data_ptr(), Us.data_ptr(), Xr.data_ptr(), Ur.data_ptr(), None,
+                None, gx.data_ptr(), gu.data_ptr(), w9.data_ptr(), None, xr.data_ptr(), ur.data_ptr(), g0.data_ptr(),
+                go.data_ptr(), gdbt.data_ptr(), workg.data_ptr(), wbg, status.data_ptr(), stream),
+                "dtmpc_solve_backward_dbas")
+
+        assert lib.dtmpc_solve_backward_dbas_workspace_bytes(_abi.F32, N, B) == wbg
+        dfn = {"fused_dbas": fused_dbas, "fused_geom_track": fused_geom_track, "fused_dbas_track": fused_dbas_track}
+        ms.update({k: [] for k in dfn})
     for _ in range(a.rounds):
         for k, fn in wfn.items():
             ms[k].append(timed(fn, a.reps))
         ms["fused"].append(timed(fused, a.reps))
         ms["composition"].append(timed(composition, a.reps))
         ms["fused_geom"].append(timed(fused_geom, a.reps))
+        for k, fn in dfn.items():  # fused_dbas right after its twin fused_geom, then the tracking pair
+            ms[k].append(timed(fn, a.reps))
         ms["composition_geom"].append(timed(composition_geom, a.reps))
         ms["layer_forward"].append(timed(layer_forward, max(a.reps // 4, 3)))
         ms["layer_backward"].append(timed(layer_backward, max(a.reps // 4, 3)))
@@ -266,6 +312,16 @@ def main():
                                                    same(outs["solve_shared"], outs["solve_scenes"])),
             "forward_mean_iters": {k: round(float(v[2].float().mean()), 3) for k, v in outs.items()},
             "forward_status_nonzero": {k: int((v[3] != 0).sum()) for k, v in outs.items()}}
+    if a.dbas:
+        for fn in dfn.values():
+            fn()
+        torch.cuda.synchronize()
+        bits = lambda p, q: all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(p, q))  # noqa: E731
+        rec["dbas"] = {"bytes_added_per_traj_and_launch_by_construction": 8,
+                       "flagged": int((status != 0).sum()),
+                       "rows_bitwise_geom": bool(bits((gwg, gtg, gx0, gob), (gwd, gtd, gx0d, gobd))),
+                       "track_rows_bitwise_geom": bool(bits(trk["geom"], trk["dbas"])),
+                       "alpha_rows_nonzero": int((gdb[0] != 0).sum()), "gamma_row_abs_max": float(gdb[1].abs().max())}
     for n, v in ms.items():
         rec[n] = {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
                   "spread": round(max(v) - min(v), 4)}
@@ -279,6 +335,11 @@ def main():
             "solve_weights / solve_shared": round(med("solve_weights") / med("solve_shared"), 4),
             "fused_weights / fused": round(med("fused_weights") / med("fused"), 4),
             "fused_geom_weights / fused_geom": round(med("fused_geom_weights") / med("fused_geom"), 4)}
+    if a.dbas:
+        med = lambda k: rec[k]["ms_median"]  # noqa: E731
+        rec["dbas"]["ratio_of_medians"] = {"fused_dbas / fused_geom": round(med("fused_dbas") / med("fused_geom"), 4),
+                                           "fused_dbas_track / fused_geom_track":
+                                               round(med("fused_dbas_track") / med("fused_geom_track"), 4)}
     line = json.dumps(rec)
     print(line, flush=True)
     if a.out:
