@@ -6,7 +6,9 @@ the paper configuration), csrc/dtmpc_fast_ilqr.hip (its solver as the standalone
 general path's solves on it), csrc/dtmpc_fast_scenes.hip (both with per-trajectory scenes), csrc/dtmpc_fast_own.hip (the tube step with
 per-trajectory ancillary weights), csrc/dtmpc_fast_weights.hip (the standalone iLQR with per-trajectory cost weights),
 csrc/dtmpc_fast_layer.hip (the differentiable solve's backward), csrc/dtmpc_fast_layer_dbas.hip (its rows w.r.t. the
-DBaS alpha / gamma: that file's text, the DBAS family), csrc/dtmpc_general.hip (general IFT
+DBaS alpha / gamma: that file's text, the DBAS family), csrc/dtmpc_fast_tight.hip and csrc/dtmpc_fast_layer_tight.hip
+(the standalone iLQR with a per-trajectory constraint tightening and its backward, the TIGHT family),
+csrc/dtmpc_general.hip (general IFT
 path), csrc/dtmpc_receding.hip (receding-horizon nominal MPC driver), csrc/dtmpc_control.hip (tanh-box
 control map + cost derivatives), csrc/dtmpc_ocp.hip (tape cost of core/ocp.py), csrc/dtmpc_systems.hip
 (per-point kernels of the reference's per-function API: dynamics, h, barriers, Jacobians, clamp, cost
@@ -23,7 +25,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", f)
         for f in ("dtmpc_kernels.hip", "dtmpc_fast.hip", "dtmpc_fast_ilp.hip", "dtmpc_fast64.hip", "dtmpc_fast64_ilp.hip",
-                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_fast_weights.hip", "dtmpc_fast_layer.hip", "dtmpc_fast_layer_dbas.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
+                  "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_fast_weights.hip", "dtmpc_fast_tight.hip", "dtmpc_fast_layer.hip", "dtmpc_fast_layer_dbas.hip", "dtmpc_fast_layer_tight.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
                   "dtmpc_control.hip", "dtmpc_ocp.hip", "dtmpc_systems.hip")]
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("dtmpc_device.hpp", "dtmpc_solver.hpp", "dtmpc_general.hpp",
                                                  "dtmpc_host.hpp", "dtmpc_ls_pk.hpp",
@@ -41,11 +43,11 @@ FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno-
 # and the f32 standalone-iLQR / receding unit (config 2 -1.3 %, receding -0.8 %; its f64 twin lost 1.2 % and keeps the
 # default) and the f32 general-path unit (general IFT step -1.1 %); the per-trajectory-scenes unit follows its
 # shared twins: the one- and two-lane tube kernels and every standalone-iLQR form are built with it there (its
-# four-lane tube kernels ride along, not measured apart), and the own-theta and per-trajectory-weights units follow the
-# scenes unit
+# four-lane tube kernels ride along, not measured apart), and the own-theta, per-trajectory-weights and
+# per-trajectory-tightening units follow the scenes unit
 UNIT_FLAGS = {u: ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
               for u in ("dtmpc_fast_ilp", "dtmpc_fast64_ilp", "dtmpc_fast_ilqr", "dtmpc_fast_general",
-                        "dtmpc_fast_scenes", "dtmpc_fast_own", "dtmpc_fast_weights")}
+                        "dtmpc_fast_scenes", "dtmpc_fast_own", "dtmpc_fast_weights", "dtmpc_fast_tight")}
 
 
 def _lib_key() -> str:
@@ -65,13 +67,13 @@ def up_to_date() -> bool:
 
 
 FAST = os.path.join(HERE, "csrc", "dtmpc_fast.hip")  # included by dtmpc_fast_ilqr.hip / dtmpc_fast_general.hip
-LAYER = os.path.join(HERE, "csrc", "dtmpc_fast_layer.hip")  # included by dtmpc_fast_layer_dbas.hip
+LAYER = os.path.join(HERE, "csrc", "dtmpc_fast_layer.hip")  # included by dtmpc_fast_layer_dbas.hip / _tight.hip
 
 
 def _key(cmd, src) -> str:
     h = hashlib.sha256(" ".join(cmd).encode())
     for p in [src, *DEPS, *([FAST] if os.path.basename(src).startswith("dtmpc_fast") else []),
-              *([LAYER] if os.path.basename(src) == "dtmpc_fast_layer_dbas.hip" else [])]:
+              *([LAYER] if os.path.basename(src) in ("dtmpc_fast_layer_dbas.hip", "dtmpc_fast_layer_tight.hip") else [])]:
         h.update(open(p, "rb").read())
     return h.hexdigest()[:24]
 
@@ -189,8 +191,10 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # ... and the per-trajectory-weights iLQR unit (dtmpc_fast_weights): nine more per-lane values live through the whole
 # solve, beside the per-lane obstacle table of its kScene forms (profiles/r13/weights_resources.txt)
 # ... and its DBAS family's unit (dtmpc_fast_layer_dbas): two more sums (profiles/r14/layer_dbas_resources.txt)
+# ... and the per-trajectory-tightening units (dtmpc_fast_tight: one more per-lane value through the solve;
+# dtmpc_fast_layer_tight: the DBAS family with one more sum -- profiles/r15/tight_resources.txt)
 RESOURCE_CHECKED = ("dtmpc_fast64", "dtmpc_fast64_ilp", "dtmpc_fast64_ilqr", "dtmpc_fast64_general", "dtmpc_fast_layer",
-                    "dtmpc_fast_layer_dbas", "dtmpc_fast_weights")
+                    "dtmpc_fast_layer_dbas", "dtmpc_fast_layer_tight", "dtmpc_fast_tight", "dtmpc_fast_weights")
 
 
 def kernel_resources(obj: str) -> dict:

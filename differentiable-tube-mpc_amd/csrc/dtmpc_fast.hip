@@ -31,7 +31,7 @@
 // for the standalone iLQR's and the general path's instantiations (their host parts below)
 #if defined(DTMPC_FAST_ILQR_TU) || defined(DTMPC_FAST_GENERAL_TU) || defined(DTMPC_FAST_ILP_TU) || \
     defined(DTMPC_FAST_SCENES_TU) || defined(DTMPC_FAST_OWN_TU) || defined(DTMPC_FAST_LAYER_TU) || \
-    defined(DTMPC_FAST_WEIGHTS_TU)
+    defined(DTMPC_FAST_WEIGHTS_TU) || defined(DTMPC_FAST_TIGHT_TU)
 #define DTMPC_FAST_AUX_TU 1
 #endif
 // The one-lane tube kernels (the headline's form) and the f32 two-lane ones live in their own translation units
@@ -126,6 +126,12 @@ constexpr int kOwn = 512;
 // The solver is the shared ilqr<>() with the nine weights in per-lane registers; only csrc/dtmpc_fast_weights.hip
 // instantiates it (with and without kScene).
 constexpr int kWts = 1024;
+// kTightPT (f32): per-trajectory constraint tightening in the standalone iLQR (dtmpc_ilqr_solve_tight) -- set together
+// with kTight: before the table is pinned the lane fills p.tight from its own element of the tight array [B] (tight_p
+// below), so the barrier of its rollouts, line search and commit sees h(x) - s_i while the linearisation keeps the plain
+// h (h_grad).  Everything after that is the shared ilqr<>(); only csrc/dtmpc_fast_tight.hip instantiates it (with and
+// without kScene).
+constexpr int kTightPT = 2048;
 template <int M>
 struct Obs {
   static constexpr int n = M & (kTight - 1);
@@ -136,6 +142,7 @@ struct Obs {
   static constexpr bool scene = (M & kScene) != 0;
   static constexpr bool own = (M & kOwn) != 0;
   static constexpr bool wts = (M & kWts) != 0;
+  static constexpr bool tightpt = (M & kTightPT) != 0;
 };
 
 // obstacle i of the table: the registers of FP, or (kReread) loaded again at each use -- through an opaque pointer
@@ -2651,6 +2658,11 @@ __device__ __forceinline__ FCost wts_c(FCost c, const real* wt, size_t nb, int i
   c.qb = q[8 * nb];
   return c;
 }
+// kTightPT: trajectory i's own tightening -- i its index in the WHOLE batch; one coalesced load
+__device__ __forceinline__ FP tight_p(FP p, const real* tg, int i) {
+  p.tight = tg[i];
+  return p;
+}
 // kOwn: trajectory i's momentum + projected update of its own column of theta / vel [6][B] from its own gradient row
 // g (acc[1..6] after the health masking: zeros for a trajectory left out, whose momentum still decays and moves
 // theta -- the shared update at B = 1 with an empty healthy set).  The roundings are theta_update_kernel<float>'s as
@@ -3051,7 +3063,14 @@ struct IArgs {
   const real* scenes;  // [3M + 3][B] or NULL (dtmpc_ilqr_solve_scenes): read by the kScene instantiations only
   // [9][B] or NULL (dtmpc_ilqr_solve_weights): read by the kWts instantiations only.  It takes 8 of the 16 bytes of
   // tail padding IK had (its alignment is its ext-vectors' 32), so no kernel's argument block grows or moves
-  const real* weights;
+  // ... or, in the same 8 bytes, [B] (dtmpc_ilqr_solve_tight): read by the kTightPT instantiations only.  A pointer
+  // of its own was tried: every ilqr_fast_kernel's argument block grew from 800 to 832 bytes and its hidden arguments
+  // moved, so the existing kernels' code changed.  The two arrays exclude each other -- launch_ilqr_fast refuses both
+  // at once -- so one slot serves both.
+  union {
+    const real* weights;
+    const real* tight;
+  };
 };
 struct IK {
   FP p;
@@ -3096,7 +3115,10 @@ ilqr_fast_kernel(IK kk) {
   S.G.k = RA{a.ok, cb * (8u * ES), l8};
   S.X = Soa<4>{(char*)a.X, 4u * bb, L};
   S.U = Soa<2>{(char*)a.U, 2u * bb, L};
-  const FP p = Obs<ML>::scene ? pin_p<ML>(scene_p<ML>(ikargs()->p, a.scenes, nb, i)) : pin_p<ML>(ikargs()->p);
+  const FP p = Obs<ML>::tightpt
+                   ? pin_p<ML>(tight_p(Obs<ML>::scene ? scene_p<ML>(ikargs()->p, a.scenes, nb, i) : ikargs()->p, a.tight, i))
+               : Obs<ML>::scene ? pin_p<ML>(scene_p<ML>(ikargs()->p, a.scenes, nb, i))
+                                : pin_p<ML>(ikargs()->p);
   const int N = p.N;
   if (TRACK) {  // the references into records (the lanes of a trajectory split the rows; one wave: in order)
     for (int k = h; k <= N; k += P) {
@@ -3501,6 +3523,10 @@ int launch_tube_fast_own(int M, int lanes, bool scene, dim3 grid, unsigned bs, h
 // obstacles at the gamma = 0 record form, with kScene as well when `scene`): kk.a.weights set
 int launch_ilqr_fast_weights(int M, int lanes, bool track, bool scene, dim3 grid, unsigned bs, hipStream_t st,
                              const FK_NS::IK& kk);
+// the per-trajectory-tightening launches (csrc/dtmpc_fast_tight.hip: the kTight | kTightPT instantiations of the
+// standalone iLQR, M obstacles at the gamma = 0 record form, with kScene as well when `scene`): kk.a.tight set
+int launch_ilqr_fast_tight(int M, int lanes, bool track, bool scene, dim3 grid, unsigned bs, hipStream_t st,
+                           const FK_NS::IK& kk);
 #endif
 
 #ifndef DTMPC_FAST_AUX_TU  // the tube step (this file's own translation unit)
@@ -3855,13 +3881,15 @@ bool FKN(ilqr_fast_eligible)(int dtype, const dtmpc_spec* sp, const dtmpc_cost* 
 int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmpc_ilqr_cfg* cf, int64_t B, const void* x0,
                      const void* Xref, const void* Uref, void* X, void* U, void* K, void* kff, int* iters, int* status,
                      signed char* choices, void* costs, int lanes, void* work, size_t work_bytes, hipStream_t st,
-                     const void* scenes, const void* weights) {
+                     const void* scenes, const void* weights, const void* tight) {
   const int N = sp->horizon;
   if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "lanes must be 1, 2 or 4");
   if (scenes && (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0))  // dtmpc_ilqr_solve_scenes has refused these
     return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory scenes need f32 and dbas_gamma == 0");
   if (weights && (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0))  // dtmpc_ilqr_solve_weights has refused these
     return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory weights need f32 and dbas_gamma == 0");
+  if (tight && (DTMPC_FAST_F64 || sp->dbas_gamma != 0.0 || weights))  // dtmpc_ilqr_solve_tight has refused these
+    return set_err(DTMPC_ERR_BAD_ARG, "a per-trajectory tightening needs f32, dbas_gamma == 0 and no weights array");
   if (!work || work_bytes < FKN(ilqr_fast_workspace_bytes)(N, B, lanes))
     return set_err(DTMPC_ERR_BAD_ARG, "work_bytes < dtmpc_ilqr_workspace_bytes(...)");
   FK_NS::IK kk;
@@ -3888,12 +3916,13 @@ int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmp
   a.work = (real*)work;
   a.scenes = (const real*)scenes;
   a.weights = (const real*)weights;
+  if (tight) a.tight = (const real*)tight;  // the same slot: never both (refused above)
   // gamma = 0: the compact gain records and the Riccati step without the barrier state's column
   const int g0 = kk.p.gamma == 0.f ? 2 : 0;
   int64_t chunk = FKN(ilqr_fast_chunk_max)(N, lanes);
-  if (const char* e = weights ? getenv("DTMPC_FAST_CHUNK") : nullptr) {  // a smaller launch chunk, as dtmpc_tube_chunk
-    const int64_t v = atoll(e) / kBlock * kBlock;  // takes it (the weights launches only: the trajectory index must be
-    if (v > 0 && v < chunk) chunk = v;             // the batch's in every chunk, tests/test_gpu_weights.py)
+  if (const char* e = weights || tight ? getenv("DTMPC_FAST_CHUNK") : nullptr) {  // a smaller launch chunk, as
+    const int64_t v = atoll(e) / kBlock * kBlock;  // dtmpc_tube_chunk takes it (the weights / tight launches only: the
+    if (v > 0 && v < chunk) chunk = v;             // trajectory index must be the batch's in every chunk)
   }
   for (int64_t c0 = 0; c0 < B; c0 += chunk) {
     const int64_t Bc = B - c0 < chunk ? B - c0 : chunk;
@@ -3910,7 +3939,12 @@ int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmp
     const int bs = tube_block(B, lanes);
     const dim3 grid = dim3((unsigned)((Bc * lanes + bs - 1) / bs));
 #if !DTMPC_FAST_F64
-    if (a.weights) {  // per-trajectory weights (with or without scenes): the kWts kernels' unit
+    if (tight) {  // per-trajectory tightening (with or without scenes): the kTightPT kernels' unit
+      if (int r = launch_ilqr_fast_tight(sp->n_obstacles, lanes, track, a.scenes != nullptr, grid, (unsigned)bs, st, kk))
+        return r;
+      continue;
+    }
+    if (weights) {  // per-trajectory weights (with or without scenes): the kWts kernels' unit
       if (int r = launch_ilqr_fast_weights(sp->n_obstacles, lanes, track, a.scenes != nullptr, grid, (unsigned)bs, st, kk))
         return r;
       continue;
@@ -4134,6 +4168,35 @@ int launch_ilqr_fast_weights(int M, int lanes, bool track, bool scene, dim3 grid
 #undef WT_LANES
 #undef WT_T
 #undef WT_LAUNCH
+}
+
+#elif defined(DTMPC_FAST_TIGHT_TU)  // the per-trajectory-tightening iLQR kernels (csrc/dtmpc_fast_tight.hip), f32 only
+
+int launch_ilqr_fast_tight(int M, int lanes, bool track, bool scene, dim3 grid, unsigned bs, hipStream_t st,
+                           const FK_NS::IK& kk) {
+#define TG_LAUNCH(m, l, t) hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<(m), l, t, 2>), grid, dim3(bs), 0, st, kk)
+#define TG_T(m, l) \
+  if (track) TG_LAUNCH(m, l, true); else TG_LAUNCH(m, l, false);
+#define TG_LANES(m) \
+  if (lanes == 4) { TG_T(m, 4) } else if (lanes == 2) { TG_T(m, 2) } else { TG_T(m, 1) }
+#define TG_CASE(m) \
+  case m:          \
+    if (scene) { TG_LANES(m | FK_NS::kTight | FK_NS::kTightPT | FK_NS::kScene) } \
+    else { TG_LANES(m | FK_NS::kTight | FK_NS::kTightPT) } \
+    return 0;
+  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "tight iLQR unit: lanes");
+  switch (M) {
+#ifdef DTMPC_FAST_M_ONLY
+    TG_CASE(DTMPC_FAST_M_ONLY)
+#else
+    TG_CASE(1) TG_CASE(2) TG_CASE(3) TG_CASE(4) TG_CASE(5) TG_CASE(6) TG_CASE(7) TG_CASE(8)
+#endif
+    default: return set_err(DTMPC_ERR_BAD_ARG, "fast iLQR with a tightening: obstacle count not instantiated");
+  }
+#undef TG_CASE
+#undef TG_LANES
+#undef TG_T
+#undef TG_LAUNCH
 }
 
 #elif defined(DTMPC_FAST_LAYER_TU)  // the differentiable solve's backward (csrc/dtmpc_fast_layer.hip), f32 only

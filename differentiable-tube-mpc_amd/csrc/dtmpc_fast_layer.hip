@@ -38,6 +38,15 @@
 // only when the solve starts from a barrier state that is not the barrier of its position (a disturbed plant state,
 // the second of two chained solves).  The family is a translation unit of its own, csrc/dtmpc_fast_layer_dbas.hip
 // (this file included with DTMPC_FAST_LAYER_DBAS_TU: its 32 kernels compile beside this unit's 64, not after them).
+// TIGHT variant (dtmpc_solve_backward_tight, solve_backward_tight_kernel<M, TRACK, W>): the backward of a solve whose
+// barrier saw the tightened h(x) - s_i, s_i the lane's own element of a tight array [B], and the row w.r.t. s_i, the
+// eleventh of ift_gradient's terms:
+//   g_tight = -sum_{m=0..N} co_m B'(h(x_m) - s_i)
+// (oracle/oracle_general.h ift1's gs without the softplus chain).  The reference linearises with B'(h) of the PLAIN h
+// (core/tube_mpc.py:315-320 against :273-276; h_grad above), so the backward sweep is unchanged and delta_lambda of a
+// given tape does not depend on s; only geom_row's factors move to z = h - s: B'(z) in the obstacle rows, dBa(z) in
+// the alpha row, B(z) - b_k in the gamma row.  The family is the DBAS family with one more load and one more sum, a
+// translation unit of its own, csrc/dtmpc_fast_layer_tight.hip (this file included with DTMPC_FAST_LAYER_TIGHT_TU).
 // All kernels include one body text, dtmpc_fast_layer_body.hpp.
 #define DTMPC_FAST_LAYER_TU 1
 #include "dtmpc_fast.hip"
@@ -92,8 +101,10 @@ struct LKG {
 // operation -- the same differences, exp2 arguments, sum order and reciprocal, so B' is evaluated at bitwise the h that
 // jac's linearisation saw -- with the terms kept apart instead of summed into grad h.
 // Returns h(x), the smooth-min the row was evaluated at (the DBAS variant forms B and dB/da from it).
-template <int M>
-__device__ __forceinline__ real geom_row(const FP& p, real px, real py, real co, real (&acc)[3 * M]) {
+// T (the TIGHT variant): B' is evaluated at z = h(x) - p.tight instead, z is what is returned, and *cb receives
+// co * B'(z), the row's term of the tightening's sum.
+template <int M, bool T = false>
+__device__ __forceinline__ real geom_row(const FP& p, real px, real py, real co, real (&acc)[3 * M], real* cb = nullptr) {
 #pragma clang fp contract(off)
   real hh[M], dxs[M], dys[M], zmax = 0.f;
 #pragma unroll
@@ -115,8 +126,11 @@ __device__ __forceinline__ real geom_row(const FP& p, real px, real py, real co,
     se += e[i];
   }
   const real inv = frcp(se);
-  const real hv = p.neg_inv_beta * (zmax + m_log(se));
-  const real s = (co * dbarrier(p, hv)) * inv;
+  real hv = p.neg_inv_beta * (zmax + m_log(se));
+  if constexpr (T) hv = hv - p.tight;
+  const real cd = co * dbarrier(p, hv);
+  if constexpr (T) *cb = cd;
+  const real s = cd * inv;
 #pragma unroll
   for (int i = 0; i < M; ++i) {
     const real cw = s * e[i];
@@ -132,10 +146,15 @@ __global__ void __launch_bounds__(kBlock) solve_backward_kernel(LK kk) {
   constexpr bool GEOM = false;
   constexpr bool WTS = false;
   constexpr bool DBAS = false;
+  constexpr bool TIGHT = false;
   real* const gx0 = nullptr;
   real* const gob = nullptr;
   const real* const wts = nullptr;
   real* const gdb = nullptr;
+  const real* const tgt = nullptr;
+  real* const gtg = nullptr;
+  (void)tgt;
+  (void)gtg;
   (void)wts;
   (void)gdb;
 #include "dtmpc_fast_layer_body.hpp"
@@ -146,11 +165,16 @@ __global__ void __launch_bounds__(kBlock) solve_backward_geom_kernel(LKG kg) {
   constexpr bool GEOM = true;
   constexpr bool WTS = false;
   constexpr bool DBAS = false;
+  constexpr bool TIGHT = false;
   const LK& kk = kg.k;
   real* const gx0 = kg.gx0;
   real* const gob = kg.gob;
   const real* const wts = nullptr;
   real* const gdb = nullptr;
+  const real* const tgt = nullptr;
+  real* const gtg = nullptr;
+  (void)tgt;
+  (void)gtg;
   (void)wts;
   (void)gdb;
 #include "dtmpc_fast_layer_body.hpp"
@@ -165,11 +189,16 @@ __global__ void __launch_bounds__(kBlock) solve_backward_weights_kernel(LKW kw) 
   constexpr bool GEOM = G;
   constexpr bool WTS = true;
   constexpr bool DBAS = false;
+  constexpr bool TIGHT = false;
   const LK& kk = kw.g.k;
   real* const gx0 = kw.g.gx0;
   real* const gob = kw.g.gob;
   const real* const wts = kw.wts;
   real* const gdb = nullptr;
+  const real* const tgt = nullptr;
+  real* const gtg = nullptr;
+  (void)tgt;
+  (void)gtg;
   (void)gdb;
 #include "dtmpc_fast_layer_body.hpp"
 }
@@ -184,11 +213,39 @@ __global__ void __launch_bounds__(kBlock) solve_backward_dbas_kernel(LKD kd) {
   constexpr bool GEOM = true;
   constexpr bool WTS = PW;
   constexpr bool DBAS = true;
+  constexpr bool TIGHT = false;
   const LK& kk = kd.w.g.k;
   real* const gx0 = kd.w.g.gx0;
   real* const gob = kd.w.g.gob;
   const real* const wts = kd.w.wts;
   real* const gdb = kd.gdb;
+  const real* const tgt = nullptr;
+  real* const gtg = nullptr;
+  (void)wts;
+  (void)tgt;
+  (void)gtg;
+#include "dtmpc_fast_layer_body.hpp"
+}
+// ... and of a solve with a per-trajectory tightening, with the row w.r.t. it (dtmpc_solve_backward_tight): the DBAS
+// family's record and sums, g_dbas optional as g_x0 / g_obs are
+struct LKT {
+  LKD d;            // p first
+  const real* tgt;  // [B]: s_i
+  real* gtg;        // [B]
+};
+template <int M, bool TRACK, bool PW>
+__global__ void __launch_bounds__(kBlock) solve_backward_tight_kernel(LKT kt) {
+  constexpr bool GEOM = true;
+  constexpr bool WTS = PW;
+  constexpr bool DBAS = true;
+  constexpr bool TIGHT = true;
+  const LK& kk = kt.d.w.g.k;
+  real* const gx0 = kt.d.w.g.gx0;
+  real* const gob = kt.d.w.g.gob;
+  const real* const wts = kt.d.w.wts;
+  real* const gdb = kt.d.gdb;
+  const real* const tgt = kt.tgt;
+  real* const gtg = kt.gtg;
   (void)wts;
 #include "dtmpc_fast_layer_body.hpp"
 }
@@ -213,12 +270,17 @@ static size_t layer_workspace_bytes(int32_t N, int64_t B, bool geom = false) {
 }
 
 // geom: solve_backward_geom_kernel with the two further outputs (either may be NULL), else solve_backward_kernel;
-// gdb (the DBAS unit only): solve_backward_dbas_kernel, wts may then be NULL
+// gdb (the DBAS unit only): solve_backward_dbas_kernel, wts may then be NULL;
+// tgt / gtg (the TIGHT unit only): solve_backward_tight_kernel, wts and gdb may then be NULL
 static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int64_t B, const fk::LArgs& a,
                                  hipStream_t st, bool geom = false, real* gx0 = nullptr, real* gob = nullptr,
-                                 const real* wts = nullptr, real* gdb = nullptr) {
-  fk::LKD kd;
-  std::memset(&kd, 0, sizeof(kd));
+                                 const real* wts = nullptr, real* gdb = nullptr, const real* tgt = nullptr,
+                                 real* gtg = nullptr) {
+  fk::LKT kt;
+  std::memset(&kt, 0, sizeof(kt));
+  fk::LKD& kd = kt.d;
+  kt.tgt = tgt;
+  kt.gtg = gtg;
   fk::LKW& kw = kd.w;
   kd.gdb = gdb;
   fk::LKG& kg = kw.g;
@@ -243,7 +305,21 @@ static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int
 #else
 #define LY_CASES LY_CASE(1) LY_CASE(2) LY_CASE(3) LY_CASE(4) LY_CASE(5) LY_CASE(6) LY_CASE(7) LY_CASE(8)
 #endif
-#ifdef DTMPC_FAST_LAYER_DBAS_TU  // this unit holds the DBAS family alone
+#if defined(DTMPC_FAST_LAYER_TIGHT_TU)  // this unit holds the TIGHT family alone
+  if (!geom || !tgt || !gtg)
+    return set_err(DTMPC_ERR_BAD_ARG, "solve backward tight: the GEOM record, tight and g_tight are required");
+#define LY_LAUNCH(m, t)                                                                                    \
+  do {                                                                                                     \
+    if (wts) hipLaunchKernelGGL((fk::solve_backward_tight_kernel<m, t, true>), grid, dim3(bs), 0, st, kt); \
+    else hipLaunchKernelGGL((fk::solve_backward_tight_kernel<m, t, false>), grid, dim3(bs), 0, st, kt);    \
+  } while (0)
+  switch (sp->n_obstacles) {
+    LY_CASES
+    default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
+  }
+#undef LY_LAUNCH
+#elif defined(DTMPC_FAST_LAYER_DBAS_TU)  // this unit holds the DBAS family alone
+  (void)kt;
   if (!geom || !gdb) return set_err(DTMPC_ERR_BAD_ARG, "solve backward dbas: the GEOM record and g_dbas are required");
 #define LY_LAUNCH(m, t)                                                                               \
   do {                                                                                                \
@@ -256,7 +332,7 @@ static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int
   }
 #undef LY_LAUNCH
 #else
-  (void)kd;
+  (void)kt;
   if (wts) {  // per-trajectory weights: one family for both record forms
 #define LY_LAUNCH(m, t)                                                                                       \
   do {                                                                                                        \
@@ -286,7 +362,7 @@ static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int
 #endif
 #undef LY_CASES
 #undef LY_CASE
-  return check_launch(gdb ? "solve_backward_dbas_kernel" : wts ? "solve_backward_weights_kernel"
+  return check_launch(gtg ? "solve_backward_tight_kernel" : gdb ? "solve_backward_dbas_kernel" : wts ? "solve_backward_weights_kernel"
                       : geom ? "solve_backward_geom_kernel" : "solve_backward_kernel");
 }
 
@@ -297,7 +373,8 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
                                 const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
                                 void* g_x0, void* g_obs, void* work, size_t work_bytes, int32_t* status,
                                 void* stream, bool wts = false, const void* weights = nullptr, bool dbas = false,
-                                void* g_dbas = nullptr) {
+                                void* g_dbas = nullptr, bool tightf = false, const void* tight = nullptr,
+                                void* g_tight = nullptr) {
   if (!spec || !cost) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL spec or cost");
   if (B < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: batch must be >= 1");
   if (spec->horizon < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: horizon must be >= 1");
@@ -309,7 +386,8 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL X, U, gX, gU, g_w or status");
   if (wts && !weights) return set_err(DTMPC_ERR_BAD_ARG, "solve backward weights: NULL weights");
   if (dbas && !g_dbas) return set_err(DTMPC_ERR_BAD_ARG, "solve backward dbas: NULL g_dbas");
-  if (geom && !wts && !dbas && !g_x0 && !g_obs)
+  if (tightf && (!tight || !g_tight)) return set_err(DTMPC_ERR_BAD_ARG, "solve backward tight: NULL tight or g_tight");
+  if (geom && !wts && !dbas && !tightf && !g_x0 && !g_obs)
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward geom: g_x0 and g_obs both NULL (that is dtmpc_solve_backward)");
   if (cost->kind == DTMPC_COST_TRACK) {
     if (!Xref || !Uref) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: the tracking cost needs Xref and Uref");
@@ -318,7 +396,9 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward: Xref, Uref, g_xref and g_uref go with the tracking cost");
   }
   if (!work || work_bytes < layer_workspace_bytes(spec->horizon, B, geom))
-    return set_err(DTMPC_ERR_BAD_ARG, dbas ? "solve backward dbas: work_bytes < "
+    return set_err(DTMPC_ERR_BAD_ARG, tightf ? "solve backward tight: work_bytes < "
+                                               "dtmpc_solve_backward_tight_workspace_bytes(...)"
+                                      : dbas ? "solve backward dbas: work_bytes < "
                                              "dtmpc_solve_backward_dbas_workspace_bytes(...)"
                                       : wts  ? "solve backward weights: work_bytes < "
                                              "dtmpc_solve_backward_weights_workspace_bytes(...)"
@@ -341,14 +421,32 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
   a.work = (real*)work;
   a.status = status;
   return launch_solve_backward(spec, cost, B, a, (hipStream_t)stream, geom, (real*)g_x0, (real*)g_obs,
-                               (const real*)weights, (real*)g_dbas);
+                               (const real*)weights, (real*)g_dbas, (const real*)tight, (real*)g_tight);
 }
 
 }  // namespace dtmpc
 
 extern "C" {
 
-#ifdef DTMPC_FAST_LAYER_DBAS_TU
+#if defined(DTMPC_FAST_LAYER_TIGHT_TU)
+
+size_t dtmpc_solve_backward_tight_workspace_bytes(int dtype, int32_t horizon, int64_t B) {
+  if (dtype != DTMPC_F32 || horizon < 1 || B < 1) return 0;
+  return dtmpc::layer_workspace_bytes(horizon, B, true);
+}
+
+int dtmpc_solve_backward_tight(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B, const void* X,
+                               const void* U, const void* Xref, const void* Uref, const void* scenes,
+                               const void* weights, const void* tight, const void* gX, const void* gU, void* g_w,
+                               void* g_target, void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* g_dbas,
+                               void* g_tight, void* work, size_t work_bytes, int32_t* status, void* stream) {
+  // always the GEOM record; weights == NULL is the shared cost, g_dbas == NULL leaves the DBaS sums unwritten
+  return dtmpc::solve_backward_entry(true, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, g_x0, g_obs, work, work_bytes, status, stream, weights != nullptr, weights,
+                                     false, g_dbas, true, tight, g_tight);
+}
+
+#elif defined(DTMPC_FAST_LAYER_DBAS_TU)
 
 size_t dtmpc_solve_backward_dbas_workspace_bytes(int dtype, int32_t horizon, int64_t B) {
   if (dtype != DTMPC_F32 || horizon < 1 || B < 1) return 0;

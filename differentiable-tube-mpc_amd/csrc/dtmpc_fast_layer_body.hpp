@@ -12,8 +12,15 @@
 // keeps the sums g_alpha_eff += co_m dBa, g_gamma -= lam_{k+1} (B(h(x_k)) - b_k); row N adds its alpha term only.
 // With b_0 = B(h(x_0)) every B(h(x_k)) - b_k is zero on a rolled-out tape and the gamma row is rounding noise.  With
 // DBAS false every `if constexpr (DBAS)` statement is discarded.
-// No include guard: it is included four times on purpose.
+// TIGHT (solve_backward_tight_kernel, dtmpc_solve_backward_tight): a fifth constexpr bool, valid with GEOM and DBAS
+// only, with the pointers `tgt` [B] and `gtg` [B] -- the lane's own tightening s_i goes into p.tight before the table is
+// pinned; geom_row<M, true> evaluates B' at z = h(x_m) - s_i, returns z (so dBa and B of the DBAS sums are taken at z as
+// well) and hands out co_m B'(z), which the forward sweep sums into g_tight = -sum_m co_m B'(z_m).  The backward sweep
+// k = N-1..0 is untouched: the reference linearises with B'(h) of the plain h (h_grad), so delta_lambda of a given tape
+// does not depend on s.  gdb may be NULL here.  With TIGHT false every `if constexpr (TIGHT)` statement is discarded.
+// No include guard: it is included five times on purpose.
   static_assert(GEOM || !DBAS, "DBAS needs the GEOM record");
+  static_assert(DBAS || !TIGHT, "TIGHT needs the GEOM record and the DBAS sums");
   constexpr int REC = GEOM ? kGeomRec : kLayerRec;
   using LFwd = typename std::conditional<GEOM && (M > 0), LFwdInG, LFwdIn>::type;  // (M > 0: a dependent type)
   const LArgs& a = kk.a;
@@ -27,6 +34,7 @@
     p = scene_p<M>(p, a.sc, nb, i);
     if (!TRACK) c.tg = scene_tg<M>(a.sc, nb, i);
   }
+  if constexpr (TIGHT) p.tight = tgt[i];  // this trajectory's own tightening
   p = pin_p<M>(p);
   const int N = p.N;
   const real* X = a.X + i;
@@ -192,6 +200,8 @@
   (void)ga;
   (void)gg;
   (void)dba_c;
+  real gs = 0.f;  // TIGHT: sum_m co_m B'(h(x_m) - s)
+  (void)gs;
   bool ok = true;
   if constexpr (GEOM) ok = ok0;
   LFwd Fn;
@@ -239,7 +249,14 @@
       if constexpr (DBAS) {
         // the same evaluation of h(x_k): co_k dBa(h) into the alpha sum, -lam_{k+1} (B(h) - b_k) into the gamma sum
         const real co = lam - g * ln;
-        const real hv = geom_row<M>(p, F.x[0], F.x[1], co, go);
+        real hv;
+        if constexpr (TIGHT) {  // hv is h(x_k) - s, and the row's term of the tightening's sum comes with it
+          real cb;
+          hv = geom_row<M, true>(p, F.x[0], F.x[1], co, go, &cb);
+          gs += cb;
+        } else {
+          hv = geom_row<M>(p, F.x[0], F.x[1], co, go);
+        }
         const real df = hv - p.a;
         const real ta = co * (dba_c * (df * df));
         ga += hv >= p.a ? 0.f : ta;
@@ -256,12 +273,28 @@
   }
   if constexpr (GEOM) {  // row N: c_N = B'(h(x_N)) lam_N
     if constexpr (DBAS) {  // row N adds its alpha term only (co_N = lam_N; no step leaves x_N)
-      const real hv = geom_row<M>(p, X[(size_t)(4 * N) * nb], X[(size_t)(4 * N + 1) * nb], lam, go);
+      real hv;
+      if constexpr (TIGHT) {
+        real cb;
+        hv = geom_row<M, true>(p, X[(size_t)(4 * N) * nb], X[(size_t)(4 * N + 1) * nb], lam, go, &cb);
+        gs += cb;
+      } else {
+        hv = geom_row<M>(p, X[(size_t)(4 * N) * nb], X[(size_t)(4 * N + 1) * nb], lam, go);
+      }
       const real df = hv - p.a;
       const real ta = lam * (dba_c * (df * df));
       ga += hv >= p.a ? 0.f : ta;
-      gdb[i] = ga;
-      gdb[nb + i] = gg;
+      if constexpr (TIGHT) {
+        if (gdb) {
+          gdb[i] = ga;
+          gdb[nb + i] = gg;
+        }
+        gtg[i] = -gs;
+        ok = ok && finite(gs);
+      } else {
+        gdb[i] = ga;
+        gdb[nb + i] = gg;
+      }
       ok = ok && finite(ga) && finite(gg);
     } else {
       geom_row<M>(p, X[(size_t)(4 * N) * nb], X[(size_t)(4 * N + 1) * nb], lam, go);

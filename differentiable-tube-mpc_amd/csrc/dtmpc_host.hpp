@@ -201,7 +201,7 @@ size_t ilqr_fast_workspace_bytes(int N, int64_t B, int lanes);
 int launch_ilqr_fast(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmpc_ilqr_cfg* cf, int64_t B, const void* x0,
                      const void* Xref, const void* Uref, void* X, void* U, void* K, void* kff, int* iters, int* status,
                      signed char* choices, void* costs, int lanes, void* work, size_t work_bytes, hipStream_t st,
-                     const void* scenes = nullptr, const void* weights = nullptr);
+                     const void* scenes = nullptr, const void* weights = nullptr, const void* tight = nullptr);
 // per-trajectory scenes (dtmpc_fast_scenes.hip): why a scenes pointer cannot be honoured, or NULL when it can
 const char* scenes_unsupported(int dtype, const dtmpc_spec* sp, const dtmpc_ilqr_cfg* cf);
 // ... and in f64 (dtmpc_fast64_ilqr.hip)
@@ -210,7 +210,7 @@ size_t ilqr_fast_workspace_bytes64(int N, int64_t B, int lanes);
 int launch_ilqr_fast64(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmpc_ilqr_cfg* cf, int64_t B, const void* x0,
                        const void* Xref, const void* Uref, void* X, void* U, void* K, void* kff, int* iters, int* status,
                        signed char* choices, void* costs, int lanes, void* work, size_t work_bytes, hipStream_t st,
-                       const void* scenes = nullptr, const void* weights = nullptr);
+                       const void* scenes = nullptr, const void* weights = nullptr, const void* tight = nullptr);
 // the receding-horizon driver on the same solver (dtmpc_nominal_receding), f32 and f64 (dtmpc_fast*_ilqr.hip)
 bool receding_fast_eligible(int dtype, const dtmpc_spec* sp, const dtmpc_cost* c, const dtmpc_ilqr_cfg* cf);
 size_t receding_fast_workspace_bytes(int N, int64_t B);

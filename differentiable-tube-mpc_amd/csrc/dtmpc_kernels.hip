@@ -794,6 +794,39 @@ int dtmpc_ilqr_solve_weights(int dtype, const dtmpc_spec* spec, const dtmpc_cost
                           lanes, work, work_bytes, (hipStream_t)stream, scenes, weights);
 }
 
+int32_t dtmpc_tight_supported(int dtype, const dtmpc_spec* spec, const dtmpc_ilqr_cfg* cfg) {
+  return dtmpc_scenes_supported(dtype, spec, cfg);  // the kTightPT kernels exist exactly where the kScene kernels do
+}
+
+size_t dtmpc_ilqr_solve_tight_workspace_bytes(int dtype, int32_t horizon, int64_t B, int32_t lanes) {
+  return dtype == DTMPC_F32 ? dtmpc_ilqr_workspace_bytes(dtype, horizon, B, lanes) : 0;
+}
+
+int dtmpc_ilqr_solve_tight(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost,
+                           const dtmpc_ilqr_cfg* cfg, int64_t B, const void* x0, const void* Xref,
+                           const void* Uref, void* X, void* U, void* K, void* kff, int32_t* iters,
+                           int32_t* status, int8_t* choices, void* costs, int32_t lanes, void* work,
+                           size_t work_bytes, const void* scenes, const void* tight, void* stream) {
+  if (!tight) return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory tightening: NULL tight");
+  int e = check_spec(spec, B);
+  if (e) return e;
+  if ((e = check_cost(cost, Xref, Uref))) return e;
+  if ((e = check_ilqr(cfg))) return e;
+  if (!x0 || !X || !U || !K || !kff || !status) return set_err(DTMPC_ERR_BAD_ARG, "NULL array");
+  if (lanes == 0) lanes = tube_lanes_default(B, dtype);
+  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "lanes must be 0, 1, 2 or 4");
+  // never the spec's h_offset in place of (or beside) the array: an unsupported configuration is an error
+  if (scenes_unsupported(dtype, spec, cfg))
+    return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory tightening: f32, the fused configuration (smooth-min over 1 to 8 "
+                                      "obstacles, relaxed inverse barrier, h_offset 0 -- the array is the only source "
+                                      "of the tightening --, six non-zero alphas), dbas_gamma == 0 and DTMPC_FAST != 0 "
+                                      "only");
+  if (!ilqr_fast_eligible(dtype, spec, cost, cfg))
+    return set_err(DTMPC_ERR_BAD_ARG, "per-trajectory tightening: the cost must not wrap the heading error");
+  return launch_ilqr_fast(spec, cost, cfg, B, x0, Xref, Uref, X, U, K, kff, iters, status, (signed char*)choices, costs,
+                          lanes, work, work_bytes, (hipStream_t)stream, scenes, nullptr, tight);
+}
+
 size_t dtmpc_sensitivity_workspace_bytes(int dtype, int32_t horizon, int64_t B, int32_t want_lambda) {
   size_t el = dtype == DTMPC_F64 ? 8 : 4;
   size_t per = (size_t)horizon * 20 + (want_lambda ? (size_t)(horizon + 1) * 20 : 0);

@@ -275,6 +275,21 @@ PROTOTYPES = {
         [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
          C.c_size_t, P, P],
     ),
+    # per-trajectory constraint tightening [B] (beside ABI 8): dtmpc_ilqr_solve_scenes' arguments with tight after
+    # scenes; dtmpc_solve_backward_dbas' with tight after weights and g_tight after g_dbas
+    "dtmpc_tight_supported": (I32, [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcIlqrCfg)]),
+    "dtmpc_ilqr_solve_tight_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64, I32]),
+    "dtmpc_ilqr_solve_tight": (
+        C.c_int,
+        [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), C.POINTER(DtmpcIlqrCfg), I64, P, P, P, P, P, P, P, P, P, P,
+         P, I32, P, C.c_size_t, P, P, P],
+    ),
+    "dtmpc_solve_backward_tight_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64]),
+    "dtmpc_solve_backward_tight": (
+        C.c_int,
+        [C.c_int, C.POINTER(DtmpcSpec), C.POINTER(DtmpcCost), I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+         C.c_size_t, P, P],
+    ),
     "dtmpc_sensitivity_upper_workspace_bytes": (C.c_size_t, [C.c_int, I32, I64]),
     "dtmpc_ddp_sensitivity_upper": (
         C.c_int,

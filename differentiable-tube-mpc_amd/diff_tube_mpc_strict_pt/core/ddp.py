@@ -28,7 +28,7 @@ import torch
 from torch import Tensor
 
 from .. import _abi, _lib
-from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, check_weights
+from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, check_tightening, check_weights
 
 __all__ = [
     "ILQRConfig",
@@ -147,11 +147,38 @@ def rollout(problem, x0: Tensor, V: Optional[Tensor] = None, *, f=None) -> Tenso
     return from_soa(Xs)
 
 
-def dbas_init(problem: DubinsDBaSProblem, x: Tensor, scenes: Optional[Tensor] = None) -> Tensor:
+def dbas_init(problem: DubinsDBaSProblem, x: Tensor, scenes: Optional[Tensor] = None,
+              tightening: Optional[Tensor] = None) -> Tensor:
     """b0 = B(h(x0)) per trajectory (core/barrier.py:111-120).  x: [B, 3] -> [B].
-    scenes ([3M + 3, B], problem.pack_scenes): each trajectory's own obstacles instead of the problem's."""
-    _require_device(x, scenes)
+    scenes ([3M + 3, B], problem.pack_scenes): each trajectory's own obstacles instead of the problem's.
+    tightening ([B], or zero-dim / one-element for a shared value): B(h(x0) - s_i), the consistent b0 of a solve with
+    ``ilqr_solve(tightening=)`` -- smooth-min aggregation and the relaxed inverse barrier only; off the hot path,
+    composed from the h and barrier kernels of core.systems.dubins_obstacles / core.barrier (with scenes the
+    smooth-min is a few tensor operations on the device)."""
+    _require_device(x, scenes, tightening)
     B = x.shape[0]
+    if tightening is not None:
+        from .barrier import relaxed_inverse_barrier_B_alpha
+        from .systems.dubins_obstacles import h_multi_circle_obstacles
+
+        M = len(problem.obstacles)
+        if problem.obs_aggregation != "smoothmin" or problem.barrier_type != "inverse" or M < 1:
+            raise ValueError("dbas_init: a tightening needs smooth-min aggregation over at least one obstacle and the "
+                             "relaxed inverse barrier")
+        if not isinstance(tightening, Tensor) or (tightening.numel() != 1 and tuple(tightening.shape) != (B,)):
+            raise ValueError(f"dbas_init: tightening must be a tensor [{B}] or zero-dim / one-element")
+        s = tightening.detach().to(dtype=x.dtype).reshape(-1)
+        if scenes is not None:
+            check_scenes(scenes, M, B, x.dtype, x.device)
+            dx = x[:, 0] - scenes[0:M]  # [M, B]
+            dy = x[:, 1] - scenes[M:2 * M]
+            beta = float(problem.obs_beta)
+            h = -torch.logsumexp(-beta * (dx * dx + dy * dy - scenes[2 * M:3 * M]), 0) / beta
+        else:
+            h = h_multi_circle_obstacles(x[:, :3].detach().contiguous(), obstacles=list(problem.obstacles),
+                                         beta=float(problem.obs_beta))
+        return relaxed_inverse_barrier_B_alpha((h - s).contiguous(), alpha=float(problem.dbas_alpha),
+                                               eps=float(problem.dbas_eps))
     lib = _lib.load()
     spec = problem.to_c()
     xs = x[:, :3].t().contiguous()
@@ -192,6 +219,7 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
                U_ref: Optional[Tensor] = None, check: bool = True, debug_name: str = "ilqr",
                record_choices: bool = False, lanes: int = 0, record_costs: bool = False,
                scenes: Optional[Tensor] = None, weights: Optional[Tensor] = None,
+               tightening: Optional[Tensor] = None,
                f=None, f_jac=None, ctrl=None, stage_cost=None, terminal_cost=None, stage_derivs=None,
                terminal_derivs=None, feasible_fn=None, debug: bool = False):
     """Batched box-clamped iLQR (core/ddp.py:102-307).
@@ -214,8 +242,15 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
     dtmpc_scenes_supported says no.
     weights ([9, B] float32, problem.pack_weights): trajectory i solves with its own Q, R, Qf, qb (``cost``'s nine
     weights are then unused; its kind, target and wrap_angle hold); composes with ``scenes``; fused f32 solver only,
-    ValueError where dtmpc_weights_supported says no -- never the shared weights instead."""
+    ValueError where dtmpc_weights_supported says no -- never the shared weights instead.
+    tightening ([B] float32, or zero-dim / one-element: broadcast here): trajectory i's barrier sees h(x) - s_i in its
+    rollouts, line search and commit while the linearisation keeps the plain h (the reference's nominal solve,
+    core/tube_mpc.py:235-238, :315-320); x0[:, 3] is the caller's (``dbas_init(..., tightening=)``).  Composes with
+    ``scenes``, not with ``weights``; fused f32 solver only, ValueError where dtmpc_tight_supported says no
+    (dbas_gamma != 0, f64, DTMPC_FAST=0, ...) -- never an untightened solve instead."""
     if f is not None:
+        if tightening is not None:
+            raise TypeError("tightening goes with the typed form (problem / cost)")
         if scenes is not None:
             raise TypeError("scenes go with the typed form (problem / cost)")
         if weights is not None:
@@ -245,6 +280,22 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
     lib = _lib.load()
     spec, cc, ic = problem.to_c(), cost.to_c(), cfg.to_c()
     dt = x0.dtype
+    if tightening is not None:  # refused before anything runs; never an untightened solve instead
+        if weights is not None:
+            raise ValueError("per-trajectory weights together with a tightening are not built in the forward solve")
+        if not isinstance(tightening, Tensor) or (tightening.numel() != 1 and tuple(tightening.shape) != (B,)):
+            raise ValueError(f"tightening must be a tensor [{B}] or zero-dim / one-element")
+        if dt != torch.float32 or not lib.dtmpc_tight_supported(_dtype_code(x0), C.byref(spec), C.byref(ic)) \
+                or cost.wrap_angle:
+            raise ValueError("a per-trajectory tightening is not supported for this dtype / problem / line search "
+                             "(dtmpc_tight_supported: f32, smooth-min, 1..8 obstacles, inverse barrier, gamma = 0, "
+                             "six non-zero alphas, DTMPC_FAST != 0, no wrapped heading error)")
+        _require_device(tightening, scenes)
+        if tightening.numel() == 1 and B != 1 or tightening.dim() != 1:  # a shared value, broadcast on the host side
+            tightening = tightening.detach().reshape(-1).expand(B).contiguous()
+        check_tightening(tightening, B, x0.device)
+        if scenes is not None:
+            check_scenes(scenes, len(problem.obstacles), B, dt, x0.device)
     if weights is not None:  # refused before anything runs; never the shared weights instead
         if dt != torch.float32 or not lib.dtmpc_weights_supported(_dtype_code(x0), C.byref(spec), C.byref(ic)) \
                 or cost.wrap_angle:
@@ -272,7 +323,14 @@ def ilqr_solve(*, problem: Optional[DubinsDBaSProblem] = None, cost: Optional[Qu
         raise ValueError("lanes must be 0 (default), 1, 2 or 4")
     wb = int(lib.dtmpc_ilqr_workspace_bytes(_dtype_code(x0), N, B, lanes))
     work = torch.empty(max(wb, 1), dtype=torch.uint8, device=x0.device)
-    if weights is not None:
+    if tightening is not None:
+        _lib.check(lib.dtmpc_ilqr_solve_tight(_dtype_code(x0), C.byref(spec), C.byref(cc), C.byref(ic), B,
+                                              x0s.data_ptr(), _ptr(Xr), _ptr(Ur), Xs.data_ptr(), Us.data_ptr(),
+                                              Ks.data_ptr(), ks.data_ptr(), iters.data_ptr(), status.data_ptr(),
+                                              _ptr(ch), _ptr(cr), lanes, work.data_ptr(), wb, _ptr(scenes),
+                                              tightening.data_ptr(), _lib.stream_of(x0)),
+                   "dtmpc_ilqr_solve_tight")
+    elif weights is not None:
         _lib.check(lib.dtmpc_ilqr_solve_weights(_dtype_code(x0), C.byref(spec), C.byref(cc), C.byref(ic), B,
                                                 x0s.data_ptr(), _ptr(Xr), _ptr(Ur), Xs.data_ptr(), Us.data_ptr(),
                                                 Ks.data_ptr(), ks.data_ptr(), iters.data_ptr(), status.data_ptr(),

@@ -27,12 +27,20 @@ with dmax = d max(alpha, eps) / d alpha = 1 (alpha > eps), 0.5 (alpha == eps), 0
 rolled-out tape makes x' = f(x_k, u_k) to rounding).  If b_0 = B(h(x_0)) then B(h(x_k)) - b_k = 0 for every k
 whatever gamma is: the gamma row is then zero in exact arithmetic (rounding noise in f32).  It is non-zero only when
 the solve starts from a barrier state that is not the barrier of its position: a plant state after a disturbance, the
-second of two chained solves.  Gradients w.r.t. the warm start, the tightening, dbas_eps and obs_beta are not
-provided; the tightening's remains ``ift_gradient``'s.
+second of two chained solves.
+
+With a per-trajectory constraint tightening (``tightening=`` [B]: trajectory i's barrier saw h(x) - s_i, the nominal
+solve of the tube MPC, core/tube_mpc.py:235-238) the factors above are taken at z = h(x_m) - s_i -- B'(z) in the
+obstacle rows, dBa(z), B(z) - b_k -- and on request (``want_tight``) the eleventh of ``ift_gradient``'s terms is returned,
+    g_tight_i = -sum_{m=0..N} co_m B'(h(x_m) - s_i)
+(its tightening column without the softplus chain).  The reference linearises with B'(h) of the PLAIN h
+(core/tube_mpc.py:315-320 against :273-276), so delta_lambda of a given tape does not depend on s and the weight,
+reference and x0 rows keep their formulas.  Gradients w.r.t. the warm start, dbas_eps and obs_beta are not provided.
 
 Where ``dtmpc_solve_backward_supported`` says yes (f32, smooth-min, 1..8 obstacles, relaxed inverse barrier) the
 rows come from ONE launch of the fused kernel (csrc/dtmpc_fast_layer.hip; dtmpc_solve_backward_geom when x0 or
-obstacle rows are wanted, dtmpc_solve_backward_dbas when the DBaS rows are), which writes no sensitivity tape;
+obstacle rows are wanted, dtmpc_solve_backward_dbas when the DBaS rows are, dtmpc_solve_backward_tight under a
+tightening), which writes no sensitivity tape;
 elsewhere (f64, min / single aggregation, log barrier) from ``dtmpc_ddp_sensitivity_upper`` and a few tensor
 operations."""
 from __future__ import annotations
@@ -49,7 +57,8 @@ from .. import _abi, _lib
 from .barrier import barrier_and_derivative
 from .ddp import (ILQRResult, _ddp_sensitivity_upper, _dtype_code, _ptr, _require_device, from_soa, ilqr_solve,
                   raise_for_status, to_soa)
-from .problem import DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, check_weights, pack_scenes, pack_weights
+from .problem import (DubinsDBaSProblem, ILQRConfig, QuadraticCost, check_scenes, check_tightening, check_weights,
+                      pack_scenes, pack_weights)
 
 __all__ = ["SolveGradient", "solve_backward", "diff_ilqr_solve"]
 
@@ -64,6 +73,7 @@ class SolveGradient:
     U_ref: Optional[Tensor]    # [B, N, 2]
     status: Tensor             # [B] int32, DTMPC_ST_NONFINITE where a row is not finite
     dbas: Optional[Tensor] = None       # [B, 2]: the DBaS alpha, gamma (want_dbas)
+    tight: Optional[Tensor] = None      # [B]: the tightening s_i (want_tight)
     x0: Optional[Tensor] = None         # [B, 4] (want_x0)
     obstacles: Optional[Tensor] = None  # [B, M, 3]: (cx, cy, r) of each circle (want_obstacles)
 
@@ -136,7 +146,8 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
                    grad_V: Tensor, X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
                    scenes: Optional[Tensor] = None, check: bool = True, want_x0: bool = False,
                    want_obstacles: bool = False, weights: Optional[Tensor] = None,
-                   want_dbas: bool = False) -> SolveGradient:
+                   want_dbas: bool = False, tightening: Optional[Tensor] = None,
+                   want_tight: bool = False) -> SolveGradient:
     """The gradient of an upper loss w.r.t. the plain cost weights and the references, per trajectory, from the
     loss's gradients ``grad_X`` [B, N+1, 4] / ``grad_V`` [B, N, 2] w.r.t. the tape (X [B, N+1, 4], V [B, N, 2]).
 
@@ -164,11 +175,19 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
     composes with scenes, weights, want_x0 and want_obstacles in the one launch) or, on f64, the composition without
     scenes; like the obstacle rows they need smooth-min aggregation and the relaxed inverse barrier, else ValueError.
     On a tape whose b_0 is the barrier of its own start position the gamma row is zero up to rounding (see the module
-    docstring): it carries information only for a solve started from a disturbed or chained barrier state."""
+    docstring): it carries information only for a solve started from a disturbed or chained barrier state.
+
+    tightening ([B] float32): the tape is that of a solve whose barrier saw h(x) - s_i (``ilqr_solve(tightening=)``);
+    every row is then evaluated under the tightened h (see the module docstring) and, with want_tight, ``tight`` [B]
+    holds d loss / d s_i.  ``problem.h_offset`` stays 0: the array is the only source of s.  Fused f32 kernel only
+    (dtmpc_solve_backward_tight, any dbas_gamma; composes with scenes, weights, want_x0, want_obstacles and want_dbas in
+    the one launch): the composition paths (f64, min / single aggregation, the log barrier) raise ValueError."""
+    if want_tight and tightening is None:
+        raise ValueError("solve_backward: want_tight needs tightening ([B])")
     if cost.wrap_angle:
         raise ValueError("solve_backward: a cost with wrap_angle is not supported (the reference's sensitivity "
                          "closures carry no wrapped heading error)")
-    _require_device(X, V, grad_X, grad_V, X_ref, U_ref, scenes, weights)
+    _require_device(X, V, grad_X, grad_V, X_ref, U_ref, scenes, weights, tightening)
     B, N = X.shape[0], problem.horizon
     if X.shape != (B, N + 1, 4) or V.shape != (B, N, 2):
         raise ValueError(f"X must be [B, {N + 1}, 4] and V [B, {N}, 2]")
@@ -191,6 +210,8 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
             check_scenes(scenes, M, B, dt, dev)
         if weights is not None:
             check_weights(weights, B, dev)
+        if tightening is not None:
+            check_tightening(tightening, B, dev)
         Xs, Us, gx, gu = to_soa(X), to_soa(V.to(dt)), to_soa(grad_X.to(dt)), to_soa(grad_V.to(dt))
         Xr = to_soa(X_ref[..., :3].to(dt)) if track else None
         Ur = to_soa(U_ref.to(dt)) if track else None
@@ -201,7 +222,10 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         gx0 = torch.empty(4, B, **kw) if want_x0 else None
         gob = torch.empty(3, M, B, **kw) if want_obstacles else None
         gdb = torch.empty(2, B, **kw) if want_dbas else None
-        if want_dbas:
+        gtg = torch.empty(B, **kw) if tightening is not None else None
+        if tightening is not None:
+            wb = int(lib.dtmpc_solve_backward_tight_workspace_bytes(_dtype_code(X), N, B))
+        elif want_dbas:
             wb = int(lib.dtmpc_solve_backward_dbas_workspace_bytes(_dtype_code(X), N, B))
         elif weights is not None:
             wb = int(lib.dtmpc_solve_backward_weights_workspace_bytes(_dtype_code(X), N, B, 1 if geom else 0))
@@ -214,7 +238,11 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         head = (_dtype_code(X), C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), _ptr(Xr), _ptr(Ur),
                 _ptr(scenes), gx.data_ptr(), gu.data_ptr(), gw.data_ptr(), _ptr(gt), _ptr(gxr), _ptr(gur))
         tail = (work.data_ptr(), wb, status.data_ptr(), _lib.stream_of(X))
-        if want_dbas:  # the DBAS family: the GEOM record, weights / x0 / obstacle rows as asked for
+        if tightening is not None:  # the TIGHT family: the GEOM record, weights / x0 / obstacle / DBaS rows as asked for
+            _lib.check(lib.dtmpc_solve_backward_tight(*head[:9], _ptr(weights), tightening.data_ptr(), *head[9:],
+                                                      _ptr(gx0), _ptr(gob), _ptr(gdb), gtg.data_ptr(), *tail),
+                       "dtmpc_solve_backward_tight")
+        elif want_dbas:  # the DBAS family: the GEOM record, weights / x0 / obstacle rows as asked for
             _lib.check(lib.dtmpc_solve_backward_dbas(*head[:9], _ptr(weights), *head[9:], _ptr(gx0), _ptr(gob),
                                                      gdb.data_ptr(), *tail), "dtmpc_solve_backward_dbas")
         elif weights is not None:  # the WTS family: the plain record, or the GEOM one when x0 / obstacle rows are wanted
@@ -234,8 +262,12 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
         out = SolveGradient(weights=gw.t().contiguous(), target=None if track else gt.t().contiguous(),
                             X_ref=from_soa(gxr) if track else None, U_ref=from_soa(gur) if track else None,
                             status=status, x0=gx0.t().contiguous() if want_x0 else None, obstacles=rows,
-                            dbas=_dbas_host(problem, gdb) if want_dbas else None)
+                            dbas=_dbas_host(problem, gdb) if want_dbas else None,
+                            tight=gtg if want_tight else None)
     else:
+        if tightening is not None:
+            raise ValueError("solve_backward: a per-trajectory tightening needs the fused kernel "
+                             "(dtmpc_solve_backward_supported: f32, smooth-min, 1..8 obstacles, inverse barrier)")
         if weights is not None:
             raise ValueError("solve_backward: per-trajectory weights need the fused kernel "
                              "(dtmpc_solve_backward_supported: f32, smooth-min, 1..8 obstacles, inverse barrier)")
@@ -285,17 +317,20 @@ def solve_backward(*, problem: DubinsDBaSProblem, cost: QuadraticCost, X: Tensor
 class _Solve(torch.autograd.Function):
     """X*, V* of a finished solve as functions of the weight / reference tensors (and, named in ``wrt``, of the
     start state and the obstacle circles: x0 / obstacles are None otherwise; dbas_alpha / dbas_gamma: the layer's
-    arguments of those names or None): forward hands the tape through, backward is solve_backward at that tape."""
+    arguments of those names or None; tight: the packed [B] tightening the solve ran with, tightening: the layer's
+    argument it came from): forward hands the tape through, backward is solve_backward at that tape."""
 
     @staticmethod
     def forward(ctx, X, V, problem, cost, scenes, per_traj_target, nref, Q, R, Qf, qb, target, X_ref, U_ref,
-                x0=None, obstacles=None, weights=None, dbas_alpha=None, dbas_gamma=None):
+                x0=None, obstacles=None, weights=None, dbas_alpha=None, dbas_gamma=None, tight=None, tightening=None):
         ctx.problem, ctx.cost, ctx.scenes = problem, cost, scenes
         ctx.weights = weights  # [9, B] packed (detached) or None: Q, R, Qf, qb are then [B, .] and get their rows
         ctx.per_traj_target, ctx.nref = per_traj_target, nref
         ctx.shapes = tuple(None if t is None else (t.shape, t.dtype)
                            for t in (Q, R, Qf, qb, target, X_ref, U_ref, x0, obstacles))
         ctx.dbas_shapes = tuple(None if t is None else (t.shape, t.dtype) for t in (dbas_alpha, dbas_gamma))
+        ctx.tight = tight  # [B] float32 (detached) or None
+        ctx.tight_shape = None if tightening is None else (tightening.shape, tightening.dtype)
         ctx.save_for_backward(X, V, *(t for t in (X_ref, U_ref) if t is not None))
         ctx.flagged = None
         return X.clone(), V.clone()
@@ -315,7 +350,8 @@ class _Solve(torch.autograd.Function):
                            U_ref=None if Ur is None else Ur.detach(), scenes=ctx.scenes, weights=ctx.weights,
                            check=False,
                            want_x0=sh[7] is not None and need[7], want_obstacles=sh[8] is not None and need[8],
-                           want_dbas=any(need_db))
+                           want_dbas=any(need_db), tightening=ctx.tight,
+                           want_tight=ctx.tight is not None and need[13])
         keep = (g.status == 0)
         ctx.flagged = g.status  # [B] int32: the trajectories left out of this backward
 
@@ -349,7 +385,12 @@ class _Solve(torch.autograd.Function):
             for j in range(2):
                 if need_db[j]:
                     gdb[j] = d[j].reshape(dsh[j][0]).to(dsh[j][1])
-        return (None,) * 7 + tuple(out) + (None,) + tuple(gdb)
+        gtg = None
+        if g.tight is not None:  # [B]: the rows, unsummed; a shared value: the sum of the unflagged trajectories' rows
+            t = rows(g.tight)
+            tsh, tdt = ctx.tight_shape
+            gtg = (t.sum(0) if tsh.numel() == 1 else t).reshape(tsh).to(tdt)
+        return (None,) * 7 + tuple(out) + (None,) + tuple(gdb) + (None, gtg)
 
 
 @dataclass(frozen=True)
@@ -368,7 +409,7 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
                     X_ref: Optional[Tensor] = None, U_ref: Optional[Tensor] = None,
                     obstacles: Optional[Tensor] = None, lanes: int = 0, check: bool = True,
                     wrt: Sequence[str] = (), dbas_alpha: Optional[Tensor] = None,
-                    dbas_gamma: Optional[Tensor] = None) -> ILQRResult:
+                    dbas_gamma: Optional[Tensor] = None, tightening: Optional[Tensor] = None) -> ILQRResult:
     """``ilqr_solve`` whose X* / V* are differentiable w.r.t. Q [3], R [2], Qf [3], qb [], the target ([3] shared
     or [B, 3] per trajectory; kind 'target') and X_ref [B, N+1, >=3] / U_ref [B, N, 2] (kind 'track').
 
@@ -404,6 +445,15 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
     a solve whose b_0 is the barrier of its start position the gamma gradient is zero up to rounding: it carries
     information for a disturbed or chained start state.  A [B] tensor is refused: per-trajectory DBaS parameters
     are not built (they would need forward kernels).  Passing neither leaves every path as it is.
+
+    tightening (opt-in): a [B] tensor (trajectory i's barrier sees h(x) - s_i) or a zero-dim / one-element tensor (one
+    s for the batch), used in the forward (``ilqr_solve(tightening=)``) and the backward
+    (``solve_backward(tightening=)``).  If it requires grad a [B] tensor receives the unsummed rows (flagged
+    trajectories zero), a shared one the sum over the unflagged trajectories; a softplus parameterisation is the
+    caller's, in torch.  x0[:, 3] is the caller's: ``dbas_init(problem, x, tightening=)`` gives the consistent
+    B(h(x_0) - s_i).  float32 on a configuration ``dtmpc_tight_supported`` accepts; refused together with
+    per-trajectory weights and with a non-zero ``problem.dbas_gamma`` / ``dbas_gamma=`` (the tightened forward has
+    neither).  Composes with ``wrt``, ``dbas_alpha=``, ``obstacles=`` and shared weights.
 
     Refused: without ``wrt`` gradients w.r.t. x0 and obstacles; always w.r.t. V_init (the warm start is not an
     argument of the optimum), a wrapped heading error, ``problem.dbas_*`` / ``problem.obs_beta`` as tensors (alpha
@@ -442,6 +492,17 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
             raise ValueError(f"diff_ilqr_solve: {name} must be a zero-dim or one-element tensor, got "
                              f"{tuple(t.shape)} -- per-trajectory DBaS parameters are not built (they would need "
                              "forward kernels)")
+    if tightening is not None:
+        if not isinstance(tightening, Tensor):
+            raise ValueError("diff_ilqr_solve: tightening is a tensor ([B], or zero-dim / one-element for a shared value)")
+        if tightening.numel() != 1 and tuple(tightening.shape) != (B,):
+            raise ValueError(f"diff_ilqr_solve: tightening must be [{B}] or a zero-dim / one-element tensor, got "
+                             f"{tuple(tightening.shape)}")
+        if x0.dtype != torch.float32:
+            raise ValueError("diff_ilqr_solve: a tightening needs float32 (dtmpc_tight_supported)")
+        if dbas_gamma is not None or float(problem.dbas_gamma) != 0.0:
+            raise ValueError("diff_ilqr_solve: a tightening needs dbas_gamma == 0 in the forward solve "
+                             "(dtmpc_tight_supported); solve_backward(tightening=) takes any gamma")
     # the weights' shapes (before anything needs a device): all four shared -- today's path -- or any per trajectory
     # (a one-element qb beside 1-D Q, R, Qf is the shared form, as it always was)
     shared_w = not (Q.dim() == 2 or R.dim() == 2 or Qf.dim() == 2 or (qb.dim() == 1 and qb.numel() != 1))
@@ -454,8 +515,11 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
                 raise ValueError(f"{name} must be [{k}] (shared) or [{B}, {k}] (per trajectory), got {tuple(t.shape)}")
         if tuple(qb.shape) not in ((), (B,)):
             raise ValueError(f"qb must be [] (shared) or [{B}] (per trajectory), got {tuple(qb.shape)}")
+    if tightening is not None and not shared_w:
+        raise ValueError("diff_ilqr_solve: per-trajectory weights together with a tightening are not built in the "
+                         "forward solve; solve_backward takes both")
     _require_device(x0, V_init, Q, R, Qf, qb, target, X_ref, U_ref,
-                    obstacles if isinstance(obstacles, Tensor) else None)
+                    obstacles if isinstance(obstacles, Tensor) else None, tightening)
     track = kind == "track"
     if track and (X_ref is None or U_ref is None):
         raise ValueError("kind 'track' needs X_ref and U_ref")
@@ -489,6 +553,9 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
         host = host[:-len(dbas)]
     cost = QuadraticCost(kind=kind, Q=tuple(host[0:3]), R=tuple(host[3:5]), Qf=tuple(host[5:8]), qb=host[8],
                          target=tuple(host[9:12]) if len(host) > 9 else (0.0, 0.0, 0.0))
+    tgt = None
+    if tightening is not None:  # the packed [B] array both kernels read (a shared value broadcast)
+        tgt = tightening.detach().to(device=x0.device, dtype=torch.float32).reshape(-1).expand(B).contiguous()
     scenes = None
     if per_traj or obstacles is not None:
         obs = obstacles
@@ -502,10 +569,10 @@ def diff_ilqr_solve(*, problem: DubinsDBaSProblem, cfg: ILQRConfig, kind: str, Q
     res = ilqr_solve(problem=problem, cost=cost, cfg=cfg, x0=x0.detach(), V_init=V_init,
                      X_ref=None if X_ref is None else X_ref.detach(), U_ref=None if U_ref is None else U_ref.detach(),
                      check=check, debug_name="diff_ilqr_solve", lanes=lanes, scenes=scenes,
-                     **({} if wts is None else {"weights": wts}))
+                     **({} if wts is None else {"weights": wts}), **({} if tgt is None else {"tightening": tgt}))
     nref = 0 if X_ref is None else X_ref.shape[-1]
     Xd, Vd = _Solve.apply(res.X, res.V, problem, cost, scenes, per_traj, nref, Q, R, Qf, qb, target, X_ref, U_ref,
-                          x0 if wrt_x0 else None, obstacles if wrt_obs else None, wts, dbas_alpha, dbas_gamma)
+                          x0 if wrt_x0 else None, obstacles if wrt_obs else None, wts, dbas_alpha, dbas_gamma, tgt, tightening)
     fields = {f.name: getattr(res, f.name) for f in dataclasses.fields(ILQRResult)}
     fields.update(X=Xd, V=Vd)
     return DiffILQRResult(**fields, _node=Xd.grad_fn)

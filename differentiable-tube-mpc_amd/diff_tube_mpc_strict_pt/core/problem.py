@@ -368,6 +368,24 @@ def check_weights(weights, B: int, device, finite: bool = True) -> None:
         raise ValueError("weights must be finite")
 
 
+def check_tightening(tightening, B: int, device, finite: bool = True) -> None:
+    """The shape / dtype / placement contract of a per-trajectory tightening [B] (``ilqr_solve(tightening=)``,
+    ``solve_backward(tightening=)``: the kernels index it unchecked), and its finiteness (one device-to-host read;
+    ``finite=False`` skips it)."""
+    import torch
+
+    if tuple(tightening.shape) != (B,):
+        raise ValueError(f"tightening must be [{B}], got {tuple(tightening.shape)}")
+    if tightening.dtype != torch.float32:
+        raise ValueError(f"tightening must be torch.float32, got {tightening.dtype}")
+    if tightening.device.type != device.type or (device.index is not None and tightening.device.index != device.index):
+        raise ValueError(f"tightening must live on {device}, got {tightening.device}")
+    if not tightening.is_contiguous():
+        raise ValueError("tightening must be contiguous")
+    if finite and not bool(torch.isfinite(tightening).all()):
+        raise ValueError("tightening must be finite")
+
+
 def tracking_cost(theta: Sequence[float]) -> QuadraticCost:
     """Ancillary tracking cost with weights theta = (Qa, Ra, qba); terminal weight Qa
     (core/tube_mpc.py:875-894)."""

@@ -450,7 +450,7 @@ int dtmpc_tube_step_own(int dtype, const dtmpc_spec* spec, const dtmpc_tube_cfg*
  *   g_target[i] = sum_k g_xref[k][i] with r_k = target, ubar = 0.
  * It is the reference's IFT at the given tape (Gauss-Newton L_zz, active set frozen): the gradient of the solver's
  * output only where the solve has converged.  The rows w.r.t. the DBaS alpha and gamma are
- * dtmpc_solve_backward_dbas's (below); the tightening's remains dtmpc_ift_gradient's.
+ * dtmpc_solve_backward_dbas's and the tightening's dtmpc_solve_backward_tight's (both below).
  * Added beside ABI 8 (csrc/dtmpc_fast_layer.hip); discovered through dtmpc_solve_backward_supported. */
 
 /* 1 for DTMPC_F32, smooth-min aggregation over 1..8 obstacles, the relaxed inverse barrier, h_offset == 0 and an
@@ -568,6 +568,57 @@ int dtmpc_solve_backward_dbas(int dtype, const dtmpc_spec* spec, const dtmpc_cos
                               const void* weights, const void* gX, const void* gU, void* g_w, void* g_target,
                               void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* g_dbas, void* work,
                               size_t work_bytes, int32_t* status, void* stream);
+
+/* ---- per-trajectory constraint tightening in the standalone solve and its backward ---------- */
+/*
+ * `tight` is [B] f32: trajectory i's barrier sees h(x) - s_i with s_i = tight[i] (core/tube_mpc.py:235-238, the
+ * nominal solve of the tube MPC).  The reference's semantics, with its quirk: the dynamics see the tightened value
+ * everywhere -- rollout, line search, commit, f_hat's barrier row b' = B(h(x') - s) - gamma (B(h(x) - s) - b) -- while
+ * the linearisation (A, B of every backward pass, forward and differentiated) keeps B'(h) of the plain h
+ * (core/tube_mpc.py:315-320 against :273-276).  The array is the only source of s: every entry below refuses
+ * spec.h_offset != 0, as every other fused standalone entry does.  b_0 = x0[3] is the caller's; the consistent start
+ * is B(h(x_0) - s_i).  f32 fused kernels only (csrc/dtmpc_fast_tight.hip, csrc/dtmpc_fast_layer_tight.hip); the tube
+ * step, the receding driver and the generic kernels take no tight array.  Added beside ABI 8. */
+
+/* 1 exactly where dtmpc_scenes_supported is 1 (the forward kernels' configurations, dbas_gamma == 0 among them). */
+int32_t dtmpc_tight_supported(int dtype, const dtmpc_spec* spec, const dtmpc_ilqr_cfg* cfg);
+
+/* Scratch bytes of dtmpc_ilqr_solve_tight: dtmpc_ilqr_workspace_bytes' for DTMPC_F32, else 0. */
+size_t dtmpc_ilqr_solve_tight_workspace_bytes(int dtype, int32_t horizon, int64_t B, int32_t lanes);
+
+/* dtmpc_ilqr_solve_scenes' arguments with tight [B] after scenes; scenes may be NULL (the spec's table and the cost's
+ * target for every trajectory).  DTMPC_ERR_BAD_ARG, before any device call, for tight == NULL, where
+ * dtmpc_tight_supported is 0 (f64, dbas_gamma != 0, h_offset != 0, DTMPC_FAST=0, ...) or the cost wraps the heading:
+ * never an untightened solve instead.  There is no weights argument: per-trajectory weights and a tightening do not
+ * combine in the forward solve. */
+int dtmpc_ilqr_solve_tight(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost,
+                           const dtmpc_ilqr_cfg* cfg, int64_t B, const void* x0, const void* Xref,
+                           const void* Uref, void* X, void* U, void* K, void* kff, int32_t* iters,
+                           int32_t* status, int8_t* choices, void* costs, int32_t lanes, void* work,
+                           size_t work_bytes, const void* scenes, const void* tight, void* stream);
+
+/* The backward of a tightened solve and the row w.r.t. the tightening, the eleventh of dtmpc_ift_gradient's terms.
+ * With lam_k = dlam_k[3] and co_m = [m >= 1] lam_m - gamma [m <= N-1] lam_{m+1} (m = 0..N),
+ *   g_tight[i] = -sum_{m=0..N} co_m B'(h(x_m) - s_i)
+ * (dtmpc_ift_gradient's column DTMPC_P_TIGHT without the softplus chain, at the tape rows); the obstacle rows carry
+ * B'(h - s) in place of B'(h), g_alpha_eff carries dBa(h - s) and g_gamma B(h - s) - b_k; the Riccati and sensitivity
+ * sweeps keep B'(h) (see above), so delta_lambda of a given tape does not depend on s and g_x0, g_w, g_target, g_xref
+ * and g_uref keep their formulas.  The kernels (solve_backward_tight_kernel, csrc/dtmpc_fast_layer_tight.hip) are
+ * dtmpc_solve_backward_dbas's with one more per-lane load and sum: the same record, no further workspace. */
+
+/* Scratch bytes of dtmpc_solve_backward_tight: dtmpc_solve_backward_geom_workspace_bytes' (0 as there). */
+size_t dtmpc_solve_backward_tight_workspace_bytes(int dtype, int32_t horizon, int64_t B);
+
+/* dtmpc_solve_backward_dbas' arguments with tight [B] after weights and g_tight [B] after g_dbas.  tight == NULL or
+ * g_tight == NULL is DTMPC_ERR_BAD_ARG; weights, g_x0, g_obs and g_dbas may each be NULL.  work_bytes is held to
+ * dtmpc_solve_backward_tight_workspace_bytes; every other rule is dtmpc_solve_backward's, checked before any device
+ * call (spec.h_offset != 0 among them), and support is dtmpc_solve_backward_supported's (any dbas_gamma).  The status
+ * word also covers g_tight and the two DBaS sums (formed whether or not g_dbas is given). */
+int dtmpc_solve_backward_tight(int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
+                               const void* X, const void* U, const void* Xref, const void* Uref, const void* scenes,
+                               const void* weights, const void* tight, const void* gX, const void* gU, void* g_w,
+                               void* g_target, void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* g_dbas,
+                               void* g_tight, void* work, size_t work_bytes, int32_t* status, void* stream);
 
 
 /* ---- general (softplus / tanh parameterised) IFT path ------------------------------------ */

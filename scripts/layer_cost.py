@@ -28,7 +28,13 @@ weights add 36 B read per trajectory and launch by construction.
 and launch, the same record) to the same alternated rounds, each call timed right after its twin of the same (M, kind):
 `fused_dbas` after `fused_geom` (M = 5, target cost), and for the tracking cost `fused_geom_track` / `fused_dbas_track`
 (references = the tape's own positions and controls; both entries with g_xref / g_uref, g_x0 and g_obs passed).  The
-rows both entries write are compared bitwise here."""
+rows both entries write are compared bitwise here.
+
+--tight adds the per-trajectory-tightening entries, each timed right after its twin in the same rounds, with s = 0 for
+every trajectory so that both do the same work (compared bitwise here): `tight_fused_dbas` then `tight_fused`
+(dtmpc_solve_backward_dbas / dtmpc_solve_backward_tight, target cost, g_x0, g_obs and g_dbas passed), and the forward at
+one lane from the same zero warm start, `tight_solve_shared` then `tight_solve` (dtmpc_ilqr_solve_ws /
+dtmpc_ilqr_solve_tight).  The tightening adds 4 B read per trajectory and launch each way and 4 B written (g_tight)."""
 import argparse
 import ctypes as C
 import json
@@ -67,6 +73,7 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--weights", action="store_true", help="also time the per-trajectory-weights entries")
     ap.add_argument("--dbas", action="store_true", help="also time dtmpc_solve_backward_dbas beside its geom twins")
+    ap.add_argument("--tight", action="store_true", help="also time the per-trajectory-tightening entries at s = 0")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     dev = torch.device("cuda", 0)
@@ -258,7 +265,62 @@ def main():
         assert lib.dtmpc_solve_backward_dbas_workspace_bytes(_abi.F32, N, B) == wbg
         dfn = {"fused_dbas": fused_dbas, "fused_geom_track": fused_geom_track, "fused_dbas_track": fused_dbas_track}
         ms.update({k: [] for k in dfn})
+    tfn = {}
+    if a.tight:
+        ict = cfg.to_c()
+        s0 = torch.zeros(B, **kw)
+        tb = {k: (torch.empty(9, B, **kw), torch.empty(3, B, **kw), torch.empty(4, B, **kw), torch.empty(3 * M, B, **kw),
+                  torch.empty(2, B, **kw)) for k in ("dbas", "tight")}
+        gts = torch.empty(B, **kw)
+        tst = {k: torch.zeros(B, dtype=torch.int32, device=dev) for k in ("dbas", "tight")}
+
+        def tight_fused_dbas():
+            w9, t3, g0, go, gd = tb["dbas"]
+            _lib.check(lib.dtmpc_solve_backward_dbas(
+                _abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), None, None, None, None,
+                gx.data_ptr(), gu.data_ptr(), w9.data_ptr(), t3.data_ptr(), None, None, g0.data_ptr(), go.data_ptr(),
+                gd.data_ptr(), workg.data_ptr(), wbg, tst["dbas"].data_ptr(), stream), "dtmpc_solve_backward_dbas")
+
+        def tight_fused():
+            w9, t3, g0, go, gd = tb["tight"]
+            _lib.check(lib.dtmpc_solve_backward_tight(
+                _abi.F32, C.byref(spec), C.byref(cc), B, Xs.data_ptr(), Us.data_ptr(), None, None, None, None,
+                s0.data_ptr(), gx.data_ptr(), gu.data_ptr(), w9.data_ptr(), t3.data_ptr(), None, None, g0.data_ptr(),
+                go.data_ptr(), gd.data_ptr(), gts.data_ptr(), workg.data_ptr(), wbg, tst["tight"].data_ptr(), stream),
+                "dtmpc_solve_backward_tight")
+
+        tx0 = x0.t().contiguous()
+        tf = {k: (torch.empty(N + 1, 4, B, **kw), torch.empty(N, 2, B, **kw), torch.empty(N, 8, B, **kw),
+                  torch.empty(N, 2, B, **kw), torch.zeros(B, dtype=torch.int32, device=dev),
+                  torch.zeros(B, dtype=torch.int32, device=dev)) for k in ("shared", "tight")}
+        twb = lib.dtmpc_ilqr_solve_tight_workspace_bytes(_abi.F32, N, B, 1)
+        assert twb == lib.dtmpc_ilqr_workspace_bytes(_abi.F32, N, B, 1)
+        twork = torch.empty(twb, dtype=torch.uint8, device=dev)
+
+        def tight_solve_shared():
+            X_, U_, K_, k_, it_, st_ = tf["shared"]
+            U_.zero_()
+            st_.zero_()
+            _lib.check(lib.dtmpc_ilqr_solve_ws(
+                _abi.F32, C.byref(spec), C.byref(cc), C.byref(ict), B, tx0.data_ptr(), None, None, X_.data_ptr(),
+                U_.data_ptr(), K_.data_ptr(), k_.data_ptr(), it_.data_ptr(), st_.data_ptr(), None, None, 1,
+                twork.data_ptr(), twb, stream), "dtmpc_ilqr_solve_ws")
+
+        def tight_solve():
+            X_, U_, K_, k_, it_, st_ = tf["tight"]
+            U_.zero_()
+            st_.zero_()
+            _lib.check(lib.dtmpc_ilqr_solve_tight(
+                _abi.F32, C.byref(spec), C.byref(cc), C.byref(ict), B, tx0.data_ptr(), None, None, X_.data_ptr(),
+                U_.data_ptr(), K_.data_ptr(), k_.data_ptr(), it_.data_ptr(), st_.data_ptr(), None, None, 1,
+                twork.data_ptr(), twb, None, s0.data_ptr(), stream), "dtmpc_ilqr_solve_tight")
+
+        tfn = {"tight_fused_dbas": tight_fused_dbas, "tight_fused": tight_fused,
+               "tight_solve_shared": tight_solve_shared, "tight_solve": tight_solve}
+        ms.update({k: [] for k in tfn})
     for _ in range(a.rounds):
+        for k, fn in tfn.items():  # each entry right after its twin
+            ms[k].append(timed(fn, a.reps))
         for k, fn in wfn.items():
             ms[k].append(timed(fn, a.reps))
         ms["fused"].append(timed(fused, a.reps))
@@ -322,6 +384,19 @@ def main():
                        "rows_bitwise_geom": bool(bits((gwg, gtg, gx0, gob), (gwd, gtd, gx0d, gobd))),
                        "track_rows_bitwise_geom": bool(bits(trk["geom"], trk["dbas"])),
                        "alpha_rows_nonzero": int((gdb[0] != 0).sum()), "gamma_row_abs_max": float(gdb[1].abs().max())}
+    if a.tight:
+        for fn in tfn.values():
+            fn()
+        torch.cuda.synchronize()
+        bits = lambda p, q: all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(p, q))  # noqa: E731
+        rec["tight"] = {"bytes_added_per_traj_and_launch_by_construction": {"forward": 4, "backward": 8},
+                        "backward_rows_bitwise_dbas_at_s0": bool(bits(tb["dbas"], tb["tight"]) and
+                                                                 bits((tst["dbas"],), (tst["tight"],))),
+                        "forward_bitwise_shared_at_s0": bool(bits(tf["shared"], tf["tight"])),
+                        "backward_flagged": int((tst["tight"] != 0).sum()),
+                        "forward_status_nonzero": int((tf["tight"][5] != 0).sum()),
+                        "forward_mean_iters": round(float(tf["tight"][4].float().mean()), 3),
+                        "g_tight_abs_max": float(gts[tst["tight"] == 0].abs().max())}
     for n, v in ms.items():
         rec[n] = {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
                   "spread": round(max(v) - min(v), 4)}
@@ -340,6 +415,11 @@ def main():
         rec["dbas"]["ratio_of_medians"] = {"fused_dbas / fused_geom": round(med("fused_dbas") / med("fused_geom"), 4),
                                            "fused_dbas_track / fused_geom_track":
                                                round(med("fused_dbas_track") / med("fused_geom_track"), 4)}
+    if a.tight:
+        med = lambda k: rec[k]["ms_median"]  # noqa: E731
+        rec["tight"]["ratio_of_medians"] = {"tight_fused / tight_fused_dbas": round(med("tight_fused") / med("tight_fused_dbas"), 4),
+                                            "tight_solve / tight_solve_shared":
+                                                round(med("tight_solve") / med("tight_solve_shared"), 4)}
     line = json.dumps(rec)
     print(line, flush=True)
     if a.out:
