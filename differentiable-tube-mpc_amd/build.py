@@ -28,7 +28,7 @@ SRCS = [os.path.join(HERE, "csrc", f)
                   "dtmpc_fast64_ilqr.hip", "dtmpc_fast64_general.hip", "dtmpc_fast_ilqr.hip", "dtmpc_fast_general.hip", "dtmpc_fast_scenes.hip", "dtmpc_fast_own.hip", "dtmpc_fast_weights.hip", "dtmpc_fast_tight.hip", "dtmpc_fast_layer.hip", "dtmpc_fast_layer_dbas.hip", "dtmpc_fast_layer_tight.hip", "dtmpc_general.hip", "dtmpc_receding.hip",
                   "dtmpc_control.hip", "dtmpc_ocp.hip", "dtmpc_systems.hip")]
 DEPS = [os.path.join(HERE, "csrc", f) for f in ("dtmpc_device.hpp", "dtmpc_solver.hpp", "dtmpc_general.hpp",
-                                                 "dtmpc_host.hpp", "dtmpc_ls_pk.hpp",
+                                                 "dtmpc_host.hpp", "dtmpc_dispatch.hpp", "dtmpc_ls_pk.hpp",
                                                  "dtmpc_fast_layer_body.hpp")] + [
     os.path.join(os.path.dirname(HERE), "include", h) for h in ("dtmpc.h", "dtmpc_control.h", "dtmpc_systems.h")
 ]

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "../../include/dtmpc.h"
+#include "dtmpc_dispatch.hpp"
 #include "dtmpc_host.hpp"
 #include "dtmpc_ls_pk.hpp"
 
@@ -3529,6 +3530,67 @@ int launch_ilqr_fast_tight(int M, int lanes, bool track, bool scene, dim3 grid, 
                            const FK_NS::IK& kk);
 #endif
 
+// the kernels' cost block: the target cost's target, zero for a tracking cost (its references are arrays)
+static FK_NS::FCost fast_cost(const dtmpc_cost& cp, bool track) {
+  const DCost<real> c = make_cost<real>(cp);
+  return FK_NS::FCost{c.Q0, c.Q1, c.Q2, c.R0, c.R1, c.Qf0, c.Qf1, c.Qf2, c.qb,
+                      track ? FK_NS::f4{0.f, 0.f, 0.f, 0.f} : FK_NS::f4{c.t0, c.t1, c.t2, 0.f}};
+}
+
+// Which tube_fast_kernel<M | FLAGS, L, G> a unit holds.  The record form G is 0, 1 or 2 at every lane count L and 3 or
+// 4 (the sin / cos cache, sparse state rows) at one lane in f32 only; the units of the flagged kernels (kScene, kOwn)
+// hold the gamma = 0 form 2 alone.  Of the plain kernels the split unit (DTMPC_FAST_ILP_TU) holds the one-lane forms
+// and, in f32, the two-lane ones, the tube step's own unit the rest -- or, in an ISA inspection build, the one form
+// -DDTMPC_FAST_ISA_ONLY=<lanes> [-DDTMPC_FAST_ISA_GM=<form>, default 2] names.
+#if defined(DTMPC_FAST_ISA_ONLY) && !defined(DTMPC_FAST_ISA_GM)
+#define DTMPC_FAST_ISA_GM 2
+#endif
+template <int FLAGS, int L, int G>
+constexpr bool tube_inst() {
+  if (FLAGS) return G == 2;
+  if (G > 2 && (L != 1 || DTMPC_FAST_F64)) return false;
+#if defined(DTMPC_FAST_ISA_ONLY)
+  return L == DTMPC_FAST_ISA_ONLY && G == DTMPC_FAST_ISA_GM;
+#elif defined(DTMPC_FAST_ILP_TU)
+  return DTMPC_FAST_ILP_SPLIT && (L == 1 || (L == 2 && DTMPC_FAST_ILP_P2));
+#else
+  return !(DTMPC_FAST_ILP_SPLIT && (L == 1 || (L == 2 && DTMPC_FAST_ILP_P2)));
+#endif
+}
+// tube_fast_kernel<M | FLAGS, lanes, g>(kk), shm bytes of dynamic LDS for the forms 3 and 4; false when this unit
+// does not hold that instantiation
+template <int FLAGS, class KK>
+static bool launch_tube_inst(int M, int lanes, int g, dim3 grid, unsigned bs, unsigned shm, hipStream_t st, const KK& kk) {
+  return pick_obstacles(M, [&](auto m) {
+    return pick<1, 2, 4>(lanes, [&](auto l) {
+      return pick<0, 1, 2, 3, 4>(g, [&](auto gm) {
+        constexpr int Mf = decltype(m)::value | FLAGS, L = decltype(l)::value, G = decltype(gm)::value;
+        if constexpr (tube_inst<FLAGS, L, G>()) {
+          hipLaunchKernelGGL((FK_NS::tube_fast_kernel<Mf, L, G>), grid, dim3(bs), G >= 3 ? shm : 0u, st, kk);
+          return true;
+        } else {
+          return false;
+        }
+      });
+    });
+  });
+}
+// ilqr_fast_kernel<M | FLAGS, lanes, track, g>(kk) with g one of GS; false when this unit does not hold it
+template <int FLAGS, bool ISA5, int... GS>
+static bool launch_ilqr_inst(int M, int lanes, bool track, int g, dim3 grid, unsigned bs, hipStream_t st,
+                             const FK_NS::IK& kk) {
+  return pick_obstacles<ISA5>(M, [&](auto m) {
+    return pick<1, 2, 4>(lanes, [&](auto l) {
+      return pick_flag(track, [&](auto t) {
+        return pick<GS...>(g, [&](auto gm) {
+          hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<decltype(m)::value | FLAGS, decltype(l)::value, decltype(t)::value,
+                                                      decltype(gm)::value>), grid, dim3(bs), 0, st, kk);
+        });
+      });
+    });
+  });
+}
+
 #ifndef DTMPC_FAST_AUX_TU  // the tube step (this file's own translation unit)
 
 // The fast kernel's configuration: f32, smooth-min over 1..8 obstacles, relaxed inverse barrier,
@@ -3635,8 +3697,7 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
   FK_NS::FK kk;
   std::memset(&kk, 0, sizeof(kk));
   fast_p(sp, kk.p);
-  const DCost<real> c = make_cost<real>(cf->nominal);
-  kk.cn = FK_NS::FCost{c.Q0, c.Q1, c.Q2, c.R0, c.R1, c.Qf0, c.Qf1, c.Qf2, c.qb, FK_NS::f4{c.t0, c.t1, c.t2, 0.f}};
+  kk.cn = fast_cost(cf->nominal, false);
   kk.cfn = fast_ilqr(cf->nom_ilqr);
   kk.cfa = fast_ilqr(cf->aux_ilqr);
   FK_NS::FArgs& a = kk.a;
@@ -3737,7 +3798,6 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
       }
     }
 #endif
-    (void)gk;
 #if !DTMPC_FAST_F64
     if (own) {  // own theta (with or without scenes): the kOwn kernels' unit, the same record form
       FK_NS::FKOwn ko;  // this chunk's arguments, then the own-theta block
@@ -3752,57 +3812,14 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
       continue;
     }
 #endif
-#define FAST_LAUNCH(m, l, g) \
-  hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) >= 3 ? shm : 0u, st, kk)
-#define FAST_LANES(m, l) \
-  if (g0 == 2) FAST_LAUNCH(m, l, 2); else if (g0) FAST_LAUNCH(m, l, 1); else FAST_LAUNCH(m, l, 0);
-#ifdef DTMPC_FAST_ISA_ONLY  // ISA inspection builds: one instantiation (lanes 1, gamma = 0 records + Riccati)
-#ifndef DTMPC_FAST_ISA_GM
-#define DTMPC_FAST_ISA_GM 2  // 3: the sin / cos cache form, 4: with sparse state rows (lanes 1)
-#endif
-#define FAST_CASE(m) \
-  case m:            \
-    FAST_LAUNCH(m, DTMPC_FAST_ISA_ONLY, DTMPC_FAST_ISA_GM); break;
-#else
-#define FAST_CASE(m)                                                                                       \
-  case m:                                                                                                  \
-    if (lanes == 4) {                                                                                      \
-      FAST_LANES(m, 4)                                                                                     \
-    } else if (lanes == 2) {                                                                               \
-      FAST_LANES_P2(m)                                                                                     \
-    } else {                                                                                               \
-      FAST_LANES_P1(m)                                                                                     \
-    }                                                                                                      \
-    break;
-#endif
-#if DTMPC_FAST_ILP_SPLIT
-#define FAST_LANES_P1(m) \
-  if (int r = FKN(launch_tube_fast_ilp)(m, 1, gk, grid, bs, shm, st, kk)) return r;
-#elif DTMPC_FAST_F64
-#define FAST_LANES_P1(m) FAST_LANES(m, 1)
-#else
-#define FAST_LANES_P1(m) \
-  if (gk == 4) FAST_LAUNCH(m, 1, 4); else if (gk == 3) FAST_LAUNCH(m, 1, 3); else { FAST_LANES(m, 1) }
-#endif
-#if DTMPC_FAST_ILP_P2
-#define FAST_LANES_P2(m) \
-  if (int r = FKN(launch_tube_fast_ilp)(m, 2, g0, grid, bs, 0u, st, kk)) return r;
-#else
-#define FAST_LANES_P2(m) FAST_LANES(m, 2)
-#endif
-    switch (sp->n_obstacles) {
-#ifdef DTMPC_FAST_M_ONLY
-      FAST_CASE(DTMPC_FAST_M_ONLY)
-#else
-      FAST_CASE(1) FAST_CASE(2) FAST_CASE(3) FAST_CASE(4) FAST_CASE(5) FAST_CASE(6) FAST_CASE(7) FAST_CASE(8)
-#endif
-      default: return set_err(DTMPC_ERR_BAD_ARG, "fast tube step: obstacle count not instantiated");
+#if DTMPC_FAST_ILP_SPLIT  // the one-lane forms and the f32 two-lane ones are the split unit's
+    if (lanes == 1 || (lanes == 2 && DTMPC_FAST_ILP_P2)) {
+      if (int r = FKN(launch_tube_fast_ilp)(sp->n_obstacles, lanes, gk, grid, bs, shm, st, kk)) return r;
+      continue;
     }
-#undef FAST_CASE
-#undef FAST_LANES_P2
-#undef FAST_LANES_P1
-#undef FAST_LANES
-#undef FAST_LAUNCH
+#endif
+    if (!launch_tube_inst<0>(sp->n_obstacles, lanes, gk, grid, (unsigned)bs, shm, st, kk))
+      return not_instantiated("fast tube step");
   }
   return check_launch("tube_fast_kernel");
 }
@@ -3812,45 +3829,10 @@ int FKN(launch_tube_fast)(const dtmpc_spec* sp, const dtmpc_tube_cfg* cf, int64_
 #if DTMPC_FAST_ILP_SPLIT
 int FKN(launch_tube_fast_ilp)(int M, int lanes, int g0, dim3 grid, unsigned bs, unsigned shm, hipStream_t st,
                               const FK_NS::FK& kk) {
-#define ILP_LAUNCH(m, l, g) \
-  hipLaunchKernelGGL((FK_NS::tube_fast_kernel<m, l, g>), grid, dim3(bs), (g) >= 3 ? shm : 0u, st, kk)
-#define ILP_LANES(m, l) \
-  if (g0 == 2) ILP_LAUNCH(m, l, 2); else if (g0) ILP_LAUNCH(m, l, 1); else ILP_LAUNCH(m, l, 0);
-#if DTMPC_FAST_F64
-#define ILP_LANES1(m) ILP_LANES(m, 1)
-#else  // f32 at one lane: g0 = 3 is the sin / cos cache form, 4 the same with sparse state rows
-#define ILP_LANES1(m) \
-  if (g0 == 4) ILP_LAUNCH(m, 1, 4); else if (g0 == 3) ILP_LAUNCH(m, 1, 3); else { ILP_LANES(m, 1) }
-#endif
-#if DTMPC_FAST_ILP_P2
-#define ILP_CASE(m)         \
-  case m:                   \
-    if (lanes == 2) {       \
-      ILP_LANES(m, 2)       \
-    } else {                \
-      ILP_LANES1(m)         \
-    }                       \
-    return 0;
-#else
-#define ILP_CASE(m) \
-  case m:           \
-    ILP_LANES1(m)   \
-    return 0;
-#endif
   if (lanes != 1 && !(DTMPC_FAST_ILP_P2 && lanes == 2)) return set_err(DTMPC_ERR_BAD_ARG, "split tube unit: lanes");
   if (g0 >= 3 && (lanes != 1 || DTMPC_FAST_F64)) return set_err(DTMPC_ERR_BAD_ARG, "split tube unit: sin / cos cache form");
-  switch (M) {
-#ifdef DTMPC_FAST_M_ONLY
-    ILP_CASE(DTMPC_FAST_M_ONLY)
-#else
-    ILP_CASE(1) ILP_CASE(2) ILP_CASE(3) ILP_CASE(4) ILP_CASE(5) ILP_CASE(6) ILP_CASE(7) ILP_CASE(8)
-#endif
-    default: return set_err(DTMPC_ERR_BAD_ARG, "fast tube step: obstacle count not instantiated");
-  }
-#undef ILP_CASE
-#undef ILP_LANES1
-#undef ILP_LANES
-#undef ILP_LAUNCH
+  if (!launch_tube_inst<0>(M, lanes, g0, grid, bs, shm, st, kk)) return not_instantiated("fast tube step");
+  return 0;
 }
 #endif
 
@@ -3895,10 +3877,8 @@ int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmp
   FK_NS::IK kk;
   std::memset(&kk, 0, sizeof(kk));
   fast_p(sp, kk.p);
-  const DCost<real> c = make_cost<real>(*cp);
   const bool track = cp->kind == DTMPC_COST_TRACK;
-  kk.c = FK_NS::FCost{c.Q0, c.Q1, c.Q2, c.R0, c.R1, c.Qf0, c.Qf1, c.Qf2, c.qb,
-                   track ? FK_NS::f4{0.f, 0.f, 0.f, 0.f} : FK_NS::f4{c.t0, c.t1, c.t2, 0.f}};
+  kk.c = fast_cost(*cp, track);
   kk.cf = fast_ilqr(*cf);
   FK_NS::IArgs& a = kk.a;
   a.B = (int)B;
@@ -3954,28 +3934,8 @@ int FKN(launch_ilqr_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const dtmp
       continue;
     }
 #endif
-#define IL_LAUNCH(m, l, t, g) hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<m, l, t, g>), grid, dim3(bs), 0, st, kk)
-#define IL_G(m, l, t) \
-  if (g0 == 2) IL_LAUNCH(m, l, t, 2); else IL_LAUNCH(m, l, t, 0);
-#define IL_T(m, l) \
-  if (track) { IL_G(m, l, true) } else { IL_G(m, l, false) }
-#define IL_CASE(m) \
-  case m:          \
-    if (lanes == 4) { IL_T(m, 4) } else if (lanes == 2) { IL_T(m, 2) } else { IL_T(m, 1) } break;
-    switch (sp->n_obstacles) {
-#if defined(DTMPC_FAST_M_ONLY)
-      IL_CASE(DTMPC_FAST_M_ONLY)
-#elif defined(DTMPC_FAST_ISA_ONLY)
-      IL_CASE(5)
-#else
-      IL_CASE(1) IL_CASE(2) IL_CASE(3) IL_CASE(4) IL_CASE(5) IL_CASE(6) IL_CASE(7) IL_CASE(8)
-#endif
-      default: return set_err(DTMPC_ERR_BAD_ARG, "fast iLQR: obstacle count not instantiated");
-    }
-#undef IL_CASE
-#undef IL_T
-#undef IL_G
-#undef IL_LAUNCH
+    if (!launch_ilqr_inst<0, true, 0, 2>(sp->n_obstacles, lanes, track, g0, grid, (unsigned)bs, st, kk))
+      return not_instantiated("fast iLQR");
   }
   return check_launch("ilqr_fast_kernel");
 }
@@ -4002,8 +3962,7 @@ int FKN(launch_receding_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const 
   FK_NS::RK kk;
   std::memset(&kk, 0, sizeof(kk));
   fast_p(sp, kk.p);
-  const DCost<real> c = make_cost<real>(*cp);
-  kk.c = FK_NS::FCost{c.Q0, c.Q1, c.Q2, c.R0, c.R1, c.Qf0, c.Qf1, c.Qf2, c.qb, FK_NS::f4{c.t0, c.t1, c.t2, 0.f}};
+  kk.c = fast_cost(*cp, false);
   kk.cf = fast_ilqr(*cf);
   FK_NS::RArgs& a = kk.a;
   a.B = (int)B;
@@ -4035,22 +3994,12 @@ int FKN(launch_receding_fast)(const dtmpc_spec* sp, const dtmpc_cost* cp, const 
     a.wsz = a.ok + (unsigned)(Bc * N * 8 * ES);
     const int bs = tube_block(B, 1);
     const dim3 grid = dim3((unsigned)((Bc + bs - 1) / bs));
-#define RC_LAUNCH(m, g) hipLaunchKernelGGL((FK_NS::receding_fast_kernel<m, g>), grid, dim3(bs), 0, st, kk)
-#define RC_CASE(m) \
-  case m:          \
-    if (g0 == 2) RC_LAUNCH(m, 2); else RC_LAUNCH(m, 0); break;
-    switch (sp->n_obstacles) {
-#if defined(DTMPC_FAST_M_ONLY)
-      RC_CASE(DTMPC_FAST_M_ONLY)
-#elif defined(DTMPC_FAST_ISA_ONLY)
-      RC_CASE(5)
-#else
-      RC_CASE(1) RC_CASE(2) RC_CASE(3) RC_CASE(4) RC_CASE(5) RC_CASE(6) RC_CASE(7) RC_CASE(8)
-#endif
-      default: return set_err(DTMPC_ERR_BAD_ARG, "fast receding: obstacle count not instantiated");
-    }
-#undef RC_CASE
-#undef RC_LAUNCH
+    const bool hit = pick_obstacles<true>(sp->n_obstacles, [&](auto m) {
+      return pick<0, 2>(g0, [&](auto g) {
+        hipLaunchKernelGGL((FK_NS::receding_fast_kernel<decltype(m)::value, decltype(g)::value>), grid, dim3(bs), 0, st, kk);
+      });
+    });
+    if (!hit) return not_instantiated("fast receding");
   }
   return check_launch("receding_fast_kernel");
 }
@@ -4075,129 +4024,56 @@ const char* scenes_unsupported(int dtype, const dtmpc_spec* sp, const dtmpc_ilqr
   return nullptr;
 }
 
-#define SC_M(m) (m | FK_NS::kScene)
 int launch_tube_fast_scenes(int M, int lanes, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FK& kk) {
-#define SC_LAUNCH(m, l) hipLaunchKernelGGL((FK_NS::tube_fast_kernel<SC_M(m), l, 2>), grid, dim3(bs), 0, st, kk)
-#define SC_CASE(m) \
-  case m:          \
-    if (lanes == 4) SC_LAUNCH(m, 4); else if (lanes == 2) SC_LAUNCH(m, 2); else SC_LAUNCH(m, 1); \
-    return 0;
   if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "scenes tube unit: lanes");
-  switch (M) {
-#ifdef DTMPC_FAST_M_ONLY
-    SC_CASE(DTMPC_FAST_M_ONLY)
-#else
-    SC_CASE(1) SC_CASE(2) SC_CASE(3) SC_CASE(4) SC_CASE(5) SC_CASE(6) SC_CASE(7) SC_CASE(8)
-#endif
-    default: return set_err(DTMPC_ERR_BAD_ARG, "fast tube step with scenes: obstacle count not instantiated");
-  }
-#undef SC_CASE
-#undef SC_LAUNCH
+  if (!launch_tube_inst<FK_NS::kScene>(M, lanes, 2, grid, bs, 0u, st, kk))
+    return not_instantiated("fast tube step with scenes");
+  return 0;
 }
 
 int launch_ilqr_fast_scenes(int M, int lanes, bool track, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::IK& kk) {
-#define SC_LAUNCH(m, l, t) hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<SC_M(m), l, t, 2>), grid, dim3(bs), 0, st, kk)
-#define SC_T(m, l) \
-  if (track) SC_LAUNCH(m, l, true); else SC_LAUNCH(m, l, false);
-#define SC_CASE(m) \
-  case m:          \
-    if (lanes == 4) { SC_T(m, 4) } else if (lanes == 2) { SC_T(m, 2) } else { SC_T(m, 1) } \
-    return 0;
   if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "scenes iLQR unit: lanes");
-  switch (M) {
-#ifdef DTMPC_FAST_M_ONLY
-    SC_CASE(DTMPC_FAST_M_ONLY)
-#else
-    SC_CASE(1) SC_CASE(2) SC_CASE(3) SC_CASE(4) SC_CASE(5) SC_CASE(6) SC_CASE(7) SC_CASE(8)
-#endif
-    default: return set_err(DTMPC_ERR_BAD_ARG, "fast iLQR with scenes: obstacle count not instantiated");
-  }
-#undef SC_CASE
-#undef SC_T
-#undef SC_LAUNCH
+  if (!launch_ilqr_inst<FK_NS::kScene, false, 2>(M, lanes, track, 2, grid, bs, st, kk))
+    return not_instantiated("fast iLQR with scenes");
+  return 0;
 }
-#undef SC_M
 
 #elif defined(DTMPC_FAST_OWN_TU)  // the own-theta tube kernels (csrc/dtmpc_fast_own.hip), f32 only
 
 int launch_tube_fast_own(int M, int lanes, bool scene, dim3 grid, unsigned bs, hipStream_t st, const FK_NS::FKOwn& kk) {
-#define OWN_LAUNCH(m, l) hipLaunchKernelGGL((FK_NS::tube_fast_kernel<(m), l, 2>), grid, dim3(bs), 0, st, kk)
-#define OWN_LANES(m) \
-  if (lanes == 4) OWN_LAUNCH(m, 4); else if (lanes == 2) OWN_LAUNCH(m, 2); else OWN_LAUNCH(m, 1);
-#define OWN_CASE(m) \
-  case m:           \
-    if (scene) { OWN_LANES(m | FK_NS::kOwn | FK_NS::kScene) } else { OWN_LANES(m | FK_NS::kOwn) } \
-    return 0;
   if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "own-theta tube unit: lanes");
-  switch (M) {
-#ifdef DTMPC_FAST_M_ONLY
-    OWN_CASE(DTMPC_FAST_M_ONLY)
-#else
-    OWN_CASE(1) OWN_CASE(2) OWN_CASE(3) OWN_CASE(4) OWN_CASE(5) OWN_CASE(6) OWN_CASE(7) OWN_CASE(8)
-#endif
-    default: return set_err(DTMPC_ERR_BAD_ARG, "fast tube step with own theta: obstacle count not instantiated");
-  }
-#undef OWN_CASE
-#undef OWN_LANES
-#undef OWN_LAUNCH
+  if (!(scene ? launch_tube_inst<FK_NS::kOwn | FK_NS::kScene>(M, lanes, 2, grid, bs, 0u, st, kk)
+              : launch_tube_inst<FK_NS::kOwn>(M, lanes, 2, grid, bs, 0u, st, kk)))
+    return not_instantiated("fast tube step with own theta");
+  return 0;
 }
 
-#elif defined(DTMPC_FAST_WEIGHTS_TU)  // the per-trajectory-weights iLQR kernels (csrc/dtmpc_fast_weights.hip), f32 only
+#elif defined(DTMPC_FAST_WEIGHTS_TU) || defined(DTMPC_FAST_TIGHT_TU)
+// the per-trajectory-weights and the per-trajectory-tightening iLQR kernels (csrc/dtmpc_fast_weights.hip,
+// csrc/dtmpc_fast_tight.hip), f32 only: the gamma = 0 record form with the unit's flags, and kScene when `scene`
 
+template <int FLAGS>
+static int launch_ilqr_flags(const char* lanes_msg, const char* who, int M, int lanes, bool track, bool scene, dim3 grid,
+                             unsigned bs, hipStream_t st, const FK_NS::IK& kk) {
+  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, lanes_msg);
+  if (!(scene ? launch_ilqr_inst<FLAGS | FK_NS::kScene, false, 2>(M, lanes, track, 2, grid, bs, st, kk)
+              : launch_ilqr_inst<FLAGS, false, 2>(M, lanes, track, 2, grid, bs, st, kk)))
+    return not_instantiated(who);
+  return 0;
+}
+#ifdef DTMPC_FAST_WEIGHTS_TU
 int launch_ilqr_fast_weights(int M, int lanes, bool track, bool scene, dim3 grid, unsigned bs, hipStream_t st,
                              const FK_NS::IK& kk) {
-#define WT_LAUNCH(m, l, t) hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<(m), l, t, 2>), grid, dim3(bs), 0, st, kk)
-#define WT_T(m, l) \
-  if (track) WT_LAUNCH(m, l, true); else WT_LAUNCH(m, l, false);
-#define WT_LANES(m) \
-  if (lanes == 4) { WT_T(m, 4) } else if (lanes == 2) { WT_T(m, 2) } else { WT_T(m, 1) }
-#define WT_CASE(m) \
-  case m:          \
-    if (scene) { WT_LANES(m | FK_NS::kWts | FK_NS::kScene) } else { WT_LANES(m | FK_NS::kWts) } \
-    return 0;
-  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "weights iLQR unit: lanes");
-  switch (M) {
-#ifdef DTMPC_FAST_M_ONLY
-    WT_CASE(DTMPC_FAST_M_ONLY)
-#else
-    WT_CASE(1) WT_CASE(2) WT_CASE(3) WT_CASE(4) WT_CASE(5) WT_CASE(6) WT_CASE(7) WT_CASE(8)
-#endif
-    default: return set_err(DTMPC_ERR_BAD_ARG, "fast iLQR with weights: obstacle count not instantiated");
-  }
-#undef WT_CASE
-#undef WT_LANES
-#undef WT_T
-#undef WT_LAUNCH
+  return launch_ilqr_flags<FK_NS::kWts>("weights iLQR unit: lanes", "fast iLQR with weights", M, lanes, track, scene, grid,
+                                        bs, st, kk);
 }
-
-#elif defined(DTMPC_FAST_TIGHT_TU)  // the per-trajectory-tightening iLQR kernels (csrc/dtmpc_fast_tight.hip), f32 only
-
+#else
 int launch_ilqr_fast_tight(int M, int lanes, bool track, bool scene, dim3 grid, unsigned bs, hipStream_t st,
                            const FK_NS::IK& kk) {
-#define TG_LAUNCH(m, l, t) hipLaunchKernelGGL((FK_NS::ilqr_fast_kernel<(m), l, t, 2>), grid, dim3(bs), 0, st, kk)
-#define TG_T(m, l) \
-  if (track) TG_LAUNCH(m, l, true); else TG_LAUNCH(m, l, false);
-#define TG_LANES(m) \
-  if (lanes == 4) { TG_T(m, 4) } else if (lanes == 2) { TG_T(m, 2) } else { TG_T(m, 1) }
-#define TG_CASE(m) \
-  case m:          \
-    if (scene) { TG_LANES(m | FK_NS::kTight | FK_NS::kTightPT | FK_NS::kScene) } \
-    else { TG_LANES(m | FK_NS::kTight | FK_NS::kTightPT) } \
-    return 0;
-  if (lanes != 1 && lanes != 2 && lanes != 4) return set_err(DTMPC_ERR_BAD_ARG, "tight iLQR unit: lanes");
-  switch (M) {
-#ifdef DTMPC_FAST_M_ONLY
-    TG_CASE(DTMPC_FAST_M_ONLY)
-#else
-    TG_CASE(1) TG_CASE(2) TG_CASE(3) TG_CASE(4) TG_CASE(5) TG_CASE(6) TG_CASE(7) TG_CASE(8)
-#endif
-    default: return set_err(DTMPC_ERR_BAD_ARG, "fast iLQR with a tightening: obstacle count not instantiated");
-  }
-#undef TG_CASE
-#undef TG_LANES
-#undef TG_T
-#undef TG_LAUNCH
+  return launch_ilqr_flags<FK_NS::kTight | FK_NS::kTightPT>("tight iLQR unit: lanes", "fast iLQR with a tightening", M,
+                                                            lanes, track, scene, grid, bs, st, kk);
 }
+#endif
 
 #elif defined(DTMPC_FAST_LAYER_TU)  // the differentiable solve's backward (csrc/dtmpc_fast_layer.hip), f32 only
 
@@ -4263,26 +4139,13 @@ int FKN(launch_general_solve_fast)(const dtmpc_spec* sp, const dtmpc_general_cfg
     a.oK = 2 * X + 2 * U;
     a.ok = a.oK + (unsigned)(Bc * N * 32 * ES);
     a.wsz = a.ok + (unsigned)(Bc * N * 8 * ES);
-#define GS_LAUNCH(m, n)                                                                                   \
-  hipLaunchKernelGGL((FK_NS::general_solve_fast_kernel<m, 1, n>), dim3((unsigned)((Bc + bs - 1) / bs)), dim3(bs), 0, \
-                     st, kk)
-#define GS_CASE(m)                 \
-  case m:                          \
-    if (nc == 4) GS_LAUNCH(m, 4);  \
-    else GS_LAUNCH(m, FK_NS::NC);     \
-    break;
-    switch (sp->n_obstacles) {
-#if defined(DTMPC_FAST_M_ONLY)
-      GS_CASE(DTMPC_FAST_M_ONLY)
-#elif defined(DTMPC_FAST_ISA_ONLY)
-      GS_CASE(5)
-#else
-      GS_CASE(1) GS_CASE(2) GS_CASE(3) GS_CASE(4) GS_CASE(5) GS_CASE(6) GS_CASE(7) GS_CASE(8)
-#endif
-      default: return set_err(DTMPC_ERR_BAD_ARG, "fast general solve: obstacle count not instantiated");
-    }
-#undef GS_CASE
-#undef GS_LAUNCH
+    const bool hit = pick_obstacles<true>(sp->n_obstacles, [&](auto m) {
+      return pick<FK_NS::NC, 4>(nc == 4 ? 4 : FK_NS::NC, [&](auto n) {
+        hipLaunchKernelGGL((FK_NS::general_solve_fast_kernel<decltype(m)::value, 1, decltype(n)::value>),
+                           dim3((unsigned)((Bc + bs - 1) / bs)), dim3(bs), 0, st, kk);
+      });
+    });
+    if (!hit) return not_instantiated("fast general solve");
   }
   return check_launch("general_solve_fast_kernel");
 }

@@ -19,12 +19,13 @@
 // choice; recomputing it in the forward sweep (sin / cos, h_grad, B': ~120 instructions against 80 B) is unmeasured.
 // The device functions are dtmpc_fast.hip's (h_grad, dbarrier, jac, vsincos, scene_p, scene_tg, pin_p) and
 // dtmpc_device.hpp / dtmpc_solver.hpp's (sens_qblocks, lu2, solve_reduced); nothing is restated here.
-// GEOM variant (dtmpc_solve_backward_geom, solve_backward_geom_kernel): the two terms that DO involve delta_lambda, the
-// rows w.r.t. the start state (g_x0 = tilde V_x[0]) and the obstacle circles.  It keeps the barrier row of V_xx and of
-// tilde V_x per step as well (25 values, 100 B), forms lam_k in the forward sweep and accumulates 3M sums (geom_row).
-// WTS variant (dtmpc_solve_backward_weights, solve_backward_weights_kernel<M, TRACK, GEOM>): the nine cost weights per
+// GEOM variant (dtmpc_solve_backward_geom, solve_backward_kernel<LKG, M, TRACK>): the two terms that DO involve
+// delta_lambda, the rows w.r.t. the start state (g_x0 = tilde V_x[0]) and the obstacle circles.  It keeps the barrier
+// row of V_xx and of tilde V_x per step as well (25 values, 100 B), forms lam_k in the forward sweep and accumulates 3M
+// sums (geom_row).
+// WTS variant (dtmpc_solve_backward_weights, solve_backward_kernel<LKW, M, TRACK, GEOM>): the nine cost weights per
 // trajectory, from a weights array [9][B] (36 B more read per trajectory); one kernel family for both record forms.
-// DBAS variant (dtmpc_solve_backward_dbas, solve_backward_dbas_kernel<M, TRACK, W>): the rows w.r.t. the barrier-state
+// DBAS variant (dtmpc_solve_backward_dbas, solve_backward_kernel<LKD, M, TRACK, W>): the rows w.r.t. the barrier-state
 // parameters alpha_eff = max(alpha, eps) and gamma, the last of ift_gradient's terms that involve delta_lambda and
 // h_offset == 0 admits.  Only the barrier row b' = B(h(x')) - gamma (B(h(x)) - b) of f_hat depends on them:
 //   g_alpha_eff = sum_{m=0..N} co_m dBa(h(x_m)),  co_m = [m >= 1] lam_m - gamma [m <= N-1] lam_{m+1},
@@ -38,7 +39,7 @@
 // only when the solve starts from a barrier state that is not the barrier of its position (a disturbed plant state,
 // the second of two chained solves).  The family is a translation unit of its own, csrc/dtmpc_fast_layer_dbas.hip
 // (this file included with DTMPC_FAST_LAYER_DBAS_TU: its 32 kernels compile beside this unit's 64, not after them).
-// TIGHT variant (dtmpc_solve_backward_tight, solve_backward_tight_kernel<M, TRACK, W>): the backward of a solve whose
+// TIGHT variant (dtmpc_solve_backward_tight, solve_backward_kernel<LKT, M, TRACK, W>): the backward of a solve whose
 // barrier saw the tightened h(x) - s_i, s_i the lane's own element of a tight array [B], and the row w.r.t. s_i, the
 // eleventh of ift_gradient's terms:
 //   g_tight = -sum_{m=0..N} co_m B'(h(x_m) - s_i)
@@ -47,7 +48,7 @@
 // given tape does not depend on s; only geom_row's factors move to z = h - s: B'(z) in the obstacle rows, dBa(z) in
 // the alpha row, B(z) - b_k in the gamma row.  The family is the DBAS family with one more load and one more sum, a
 // translation unit of its own, csrc/dtmpc_fast_layer_tight.hip (this file included with DTMPC_FAST_LAYER_TIGHT_TU).
-// All kernels include one body text, dtmpc_fast_layer_body.hpp.
+// One kernel template over the variants' argument blocks includes the body text, dtmpc_fast_layer_body.hpp.
 #define DTMPC_FAST_LAYER_TU 1
 #include "dtmpc_fast.hip"
 
@@ -73,12 +74,6 @@ struct LArgs {
   real* work;        // [N][kLayerRec][B]
   int* status;       // [B]
 };
-struct LK {
-  FP p;  // first, as in every fused kernel's argument block
-  FCost c;
-  LArgs a;
-};
-
 // one step's inputs of the backward pass / of the forward sweep, loaded one step ahead of their use
 struct LBwdIn {
   real x0, x1, x2, u0, u1, g0, g1, g2, g3, h0, h1;
@@ -89,12 +84,72 @@ struct LFwdIn {
 struct LFwdInG : LFwdIn {  // GEOM
   real L[5];  // V_xx[k][3][0..3], tilde V_x[k][3]
 };
-// GEOM (dtmpc_solve_backward_geom): the kernel's block and two more outputs
+
+// The kernels' argument blocks, one per entry point of include/dtmpc.h: each holds the one before it (`in`) with its
+// own pointers behind, so a kernel's argument offsets are those of every smaller block and the host fills the largest.
+// A block says which of GEOM / WTS / DBAS / TIGHT its kernels compile in, f being the kernel's flag FL where it has one.
+enum LVariant { kLPlain, kLGeom, kLWeights, kLDbas, kLTight };
+struct LK {
+  FP p;  // first, as in every fused kernel's argument block
+  FCost c;
+  LArgs a;
+  static constexpr int kVariant = kLPlain;
+  static constexpr bool kFlag = false, kHasDbas = false, kHasTight = false;
+  static constexpr bool has_geom(bool) { return false; }
+  static constexpr bool has_wts(bool) { return false; }
+};
+// GEOM (dtmpc_solve_backward_geom): the rows w.r.t. the start state and the obstacle circles
 struct LKG {
-  LK k;       // p first
+  LK in;
   real* gx0;  // [4][B] or NULL
   real* gob;  // [3M][B] or NULL: rows cx[0..M), cy[0..M), r2[0..M)
+  static constexpr int kVariant = kLGeom;
+  static constexpr bool kFlag = false, kHasDbas = false, kHasTight = false;
+  static constexpr bool has_geom(bool) { return true; }
+  static constexpr bool has_wts(bool) { return false; }
 };
+// WTS (dtmpc_solve_backward_weights): per-trajectory cost weights, both record forms -- FL the GEOM one
+struct LKW {
+  LKG in;
+  const real* wts;  // [9][B]: rows Q0 Q1 Q2 R0 R1 Qf0 Qf1 Qf2 qb (g_w's row order)
+  static constexpr int kVariant = kLWeights;
+  static constexpr bool kFlag = true, kHasDbas = false, kHasTight = false;
+  static constexpr bool has_geom(bool f) { return f; }
+  static constexpr bool has_wts(bool) { return true; }
+};
+// DBAS (dtmpc_solve_backward_dbas): the rows w.r.t. the DBaS parameters; always the GEOM record, FL the
+// per-trajectory-weights flag (wts is NULL without it); g_x0 / g_obs stay optional
+struct LKD {
+  LKW in;
+  real* gdb;  // [2][B]: rows alpha_eff, gamma
+  static constexpr int kVariant = kLDbas;
+  static constexpr bool kFlag = true, kHasDbas = true, kHasTight = false;
+  static constexpr bool has_geom(bool) { return true; }
+  static constexpr bool has_wts(bool f) { return f; }
+};
+// TIGHT (dtmpc_solve_backward_tight): a solve with a per-trajectory tightening and the row w.r.t. it; the DBAS family's
+// record and sums, g_dbas optional as g_x0 / g_obs are
+struct LKT {
+  LKD in;
+  const real* tgt;  // [B]: s_i
+  real* gtg;        // [B]
+  static constexpr int kVariant = kLTight;
+  static constexpr bool kFlag = true, kHasDbas = true, kHasTight = true;
+  static constexpr bool has_geom(bool) { return true; }
+  static constexpr bool has_wts(bool f) { return f; }
+};
+// The member m of block B where the kernel's block K holds a B, else NULL.  (The block goes by value: an accessor that
+// takes the kernel's argument by reference compiles to other code, as dtmpc_fast_layer_body.hpp notes.)
+template <class K, class B, class P>
+__device__ __forceinline__ P opt(const K k, P B::*m) {
+  if constexpr (std::is_same_v<K, B>) {
+    return k.*m;
+  } else if constexpr (K::kVariant > B::kVariant) {
+    return opt(k.in, m);
+  } else {
+    return nullptr;
+  }
+}
 
 // One tape row's part of the obstacle rows: acc[j], acc[M + j], acc[2M + j] += co * B'(h(x)) * w_j(x) * (-2 (px - cx_j),
 // -2 (py - cy_j), -1), w_j = softmax_j(-beta h_j).  The weights and h are h_grad<M>'s (dtmpc_fast.hip) operation for
@@ -141,112 +196,19 @@ __device__ __forceinline__ real geom_row(const FP& p, real px, real py, real co,
   return hv;
 }
 
-template <int M, bool TRACK>
-__global__ void __launch_bounds__(kBlock) solve_backward_kernel(LK kk) {
-  constexpr bool GEOM = false;
-  constexpr bool WTS = false;
-  constexpr bool DBAS = false;
-  constexpr bool TIGHT = false;
-  real* const gx0 = nullptr;
-  real* const gob = nullptr;
-  const real* const wts = nullptr;
-  real* const gdb = nullptr;
-  const real* const tgt = nullptr;
-  real* const gtg = nullptr;
-  (void)tgt;
-  (void)gtg;
-  (void)wts;
-  (void)gdb;
-#include "dtmpc_fast_layer_body.hpp"
-}
-// ... and with the rows w.r.t. the start state and the obstacle circles (dtmpc_solve_backward_geom)
-template <int M, bool TRACK>
-__global__ void __launch_bounds__(kBlock) solve_backward_geom_kernel(LKG kg) {
-  constexpr bool GEOM = true;
-  constexpr bool WTS = false;
-  constexpr bool DBAS = false;
-  constexpr bool TIGHT = false;
-  const LK& kk = kg.k;
-  real* const gx0 = kg.gx0;
-  real* const gob = kg.gob;
-  const real* const wts = nullptr;
-  real* const gdb = nullptr;
-  const real* const tgt = nullptr;
-  real* const gtg = nullptr;
-  (void)tgt;
-  (void)gtg;
-  (void)wts;
-  (void)gdb;
-#include "dtmpc_fast_layer_body.hpp"
-}
-// ... and with per-trajectory cost weights (dtmpc_solve_backward_weights): both record forms, G the GEOM one
-struct LKW {
-  LKG g;            // p first
-  const real* wts;  // [9][B]: rows Q0 Q1 Q2 R0 R1 Qf0 Qf1 Qf2 qb (g_w's row order)
-};
-template <int M, bool TRACK, bool G>
-__global__ void __launch_bounds__(kBlock) solve_backward_weights_kernel(LKW kw) {
-  constexpr bool GEOM = G;
-  constexpr bool WTS = true;
-  constexpr bool DBAS = false;
-  constexpr bool TIGHT = false;
-  const LK& kk = kw.g.k;
-  real* const gx0 = kw.g.gx0;
-  real* const gob = kw.g.gob;
-  const real* const wts = kw.wts;
-  real* const gdb = nullptr;
-  const real* const tgt = nullptr;
-  real* const gtg = nullptr;
-  (void)tgt;
-  (void)gtg;
-  (void)gdb;
-#include "dtmpc_fast_layer_body.hpp"
-}
-// ... and with the rows w.r.t. the DBaS parameters (dtmpc_solve_backward_dbas): always the GEOM record, W the
-// per-trajectory-weights flag (kd.w.wts is NULL without it); g_x0 / g_obs stay optional
-struct LKD {
-  LKW w;      // p first
-  real* gdb;  // [2][B]: rows alpha_eff, gamma
-};
-template <int M, bool TRACK, bool PW>  // PW: per-trajectory weights (the body text names the workspace W)
-__global__ void __launch_bounds__(kBlock) solve_backward_dbas_kernel(LKD kd) {
-  constexpr bool GEOM = true;
-  constexpr bool WTS = PW;
-  constexpr bool DBAS = true;
-  constexpr bool TIGHT = false;
-  const LK& kk = kd.w.g.k;
-  real* const gx0 = kd.w.g.gx0;
-  real* const gob = kd.w.g.gob;
-  const real* const wts = kd.w.wts;
-  real* const gdb = kd.gdb;
-  const real* const tgt = nullptr;
-  real* const gtg = nullptr;
-  (void)wts;
-  (void)tgt;
-  (void)gtg;
-#include "dtmpc_fast_layer_body.hpp"
-}
-// ... and of a solve with a per-trajectory tightening, with the row w.r.t. it (dtmpc_solve_backward_tight): the DBAS
-// family's record and sums, g_dbas optional as g_x0 / g_obs are
-struct LKT {
-  LKD d;            // p first
-  const real* tgt;  // [B]: s_i
-  real* gtg;        // [B]
-};
-template <int M, bool TRACK, bool PW>
-__global__ void __launch_bounds__(kBlock) solve_backward_tight_kernel(LKT kt) {
-  constexpr bool GEOM = true;
-  constexpr bool WTS = PW;
-  constexpr bool DBAS = true;
-  constexpr bool TIGHT = true;
-  const LK& kk = kt.d.w.g.k;
-  real* const gx0 = kt.d.w.g.gx0;
-  real* const gob = kt.d.w.g.gob;
-  const real* const wts = kt.d.w.wts;
-  real* const gdb = kt.d.gdb;
-  const real* const tgt = kt.tgt;
-  real* const gtg = kt.gtg;
-  (void)wts;
+// One kernel over the blocks: solve_backward_kernel<LK, M, TRACK>, <LKG, M, TRACK>, <LKW, M, TRACK, G>,
+// <LKD, M, TRACK, W> and <LKT, M, TRACK, W>.
+template <class K, int M, bool TRACK, bool FL = false>
+__global__ void __launch_bounds__(kBlock) solve_backward_kernel(K kb) {
+  constexpr bool GEOM = K::has_geom(FL), WTS = K::has_wts(FL), DBAS = K::kHasDbas, TIGHT = K::kHasTight;
+  static_assert(std::is_standard_layout_v<K>, "a block's address is that of the LK it begins with");
+  const LK& kk = reinterpret_cast<const LK&>(kb);
+  [[maybe_unused]] real* const gx0 = opt(kb, &LKG::gx0);
+  [[maybe_unused]] real* const gob = opt(kb, &LKG::gob);
+  [[maybe_unused]] const real* const wts = opt(kb, &LKW::wts);
+  [[maybe_unused]] real* const gdb = opt(kb, &LKD::gdb);
+  [[maybe_unused]] const real* const tgt = opt(kb, &LKT::tgt);
+  [[maybe_unused]] real* const gtg = opt(kb, &LKT::gtg);
 #include "dtmpc_fast_layer_body.hpp"
 }
 
@@ -269,112 +231,100 @@ static size_t layer_workspace_bytes(int32_t N, int64_t B, bool geom = false) {
   return (size_t)N * (geom ? fk::kGeomRec : fk::kLayerRec) * sizeof(real) * (size_t)B;
 }
 
-// geom: solve_backward_geom_kernel with the two further outputs (either may be NULL), else solve_backward_kernel;
-// gdb (the DBAS unit only): solve_backward_dbas_kernel, wts may then be NULL;
-// tgt / gtg (the TIGHT unit only): solve_backward_tight_kernel, wts and gdb may then be NULL
-static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int64_t B, const fk::LArgs& a,
-                                 hipStream_t st, bool geom = false, real* gx0 = nullptr, real* gob = nullptr,
-                                 const real* wts = nullptr, real* gdb = nullptr, const real* tgt = nullptr,
-                                 real* gtg = nullptr) {
-  fk::LKT kt;
-  std::memset(&kt, 0, sizeof(kt));
-  fk::LKD& kd = kt.d;
-  kt.tgt = tgt;
-  kt.gtg = gtg;
-  fk::LKW& kw = kd.w;
-  kd.gdb = gdb;
-  fk::LKG& kg = kw.g;
-  fk::LK& kk = kg.k;
-  kw.wts = wts;
-  fast_p(sp, kk.p);
-  const DCost<real> c = make_cost<real>(*cp);
-  const bool track = cp->kind == DTMPC_COST_TRACK;
-  kk.c = fk::FCost{c.Q0, c.Q1, c.Q2, c.R0, c.R1, c.Qf0, c.Qf1, c.Qf2, c.qb,
-                   track ? fk::f4{0.f, 0.f, 0.f, 0.f} : fk::f4{c.t0, c.t1, c.t2, 0.f}};
-  kk.a = a;
-  kg.gx0 = gx0;
-  kg.gob = gob;
-  const int bs = tube_block(B, 1);
-  const dim3 grid((unsigned)((B + bs - 1) / bs));
-#define LY_CASE(m) \
-  case m:          \
-    if (track) LY_LAUNCH(m, true); else LY_LAUNCH(m, false); \
-    break;
-#ifdef DTMPC_FAST_M_ONLY
-#define LY_CASES LY_CASE(DTMPC_FAST_M_ONLY)
+// What a variant adds to dtmpc_solve_backward's arguments; a pointer the variant does not have stays NULL.
+struct LayerOpt {
+  fk::LVariant variant = fk::kLPlain;
+  bool geom = false;              // the GEOM record (kGeomRec values per step) is in use
+  void* gx0 = nullptr;            // g_x0 [4][B]
+  void* gob = nullptr;            // g_obs [3M][B]
+  const void* weights = nullptr;  // [9][B]
+  void* gdb = nullptr;            // g_dbas [2][B]
+  const void* tight = nullptr;    // [B]
+  void* gtg = nullptr;            // g_tight [B]
+};
+// per variant: the kernel as check_launch names it, and the message of a workspace that is too small
+static const char* const kLayerKernel[] = {"solve_backward_kernel<LK>", "solve_backward_kernel<LKG>",
+                                           "solve_backward_kernel<LKW>", "solve_backward_kernel<LKD>",
+                                           "solve_backward_kernel<LKT>"};
+static const char* const kLayerWorkMsg[] = {
+    "solve backward: work_bytes < dtmpc_solve_backward_workspace_bytes(...)",
+    "solve backward geom: work_bytes < dtmpc_solve_backward_geom_workspace_bytes(...)",
+    "solve backward weights: work_bytes < dtmpc_solve_backward_weights_workspace_bytes(...)",
+    "solve backward dbas: work_bytes < dtmpc_solve_backward_dbas_workspace_bytes(...)",
+    "solve backward tight: work_bytes < dtmpc_solve_backward_tight_workspace_bytes(...)"};
+
+// The blocks whose kernels this unit instantiates: the DBAS and the TIGHT family (32 kernels each) are units of their
+// own, so that they compile beside this unit's 64 kernels, not after them.
+template <class... K>
+struct Blocks {};
+#if defined(DTMPC_FAST_LAYER_TIGHT_TU)
+using UnitBlocks = Blocks<fk::LKT>;
+#elif defined(DTMPC_FAST_LAYER_DBAS_TU)
+using UnitBlocks = Blocks<fk::LKD>;
 #else
-#define LY_CASES LY_CASE(1) LY_CASE(2) LY_CASE(3) LY_CASE(4) LY_CASE(5) LY_CASE(6) LY_CASE(7) LY_CASE(8)
+using UnitBlocks = Blocks<fk::LK, fk::LKG, fk::LKW>;
 #endif
-#if defined(DTMPC_FAST_LAYER_TIGHT_TU)  // this unit holds the TIGHT family alone
-  if (!geom || !tgt || !gtg)
-    return set_err(DTMPC_ERR_BAD_ARG, "solve backward tight: the GEOM record, tight and g_tight are required");
-#define LY_LAUNCH(m, t)                                                                                    \
-  do {                                                                                                     \
-    if (wts) hipLaunchKernelGGL((fk::solve_backward_tight_kernel<m, t, true>), grid, dim3(bs), 0, st, kt); \
-    else hipLaunchKernelGGL((fk::solve_backward_tight_kernel<m, t, false>), grid, dim3(bs), 0, st, kt);    \
-  } while (0)
-  switch (sp->n_obstacles) {
-    LY_CASES
-    default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
+
+// solve_backward_kernel<K, M, track[, FL]> on the K that kt begins with
+template <class K>
+static int launch_block(const fk::LKT& kt, int M, bool track, const LayerOpt& o, dim3 grid, int bs, hipStream_t st) {
+  if constexpr (K::kHasTight) {
+    if (!o.geom || !o.tight || !o.gtg)
+      return set_err(DTMPC_ERR_BAD_ARG, "solve backward tight: the GEOM record, tight and g_tight are required");
+  } else if constexpr (K::kHasDbas) {
+    if (!o.geom || !o.gdb)
+      return set_err(DTMPC_ERR_BAD_ARG, "solve backward dbas: the GEOM record and g_dbas are required");
   }
-#undef LY_LAUNCH
-#elif defined(DTMPC_FAST_LAYER_DBAS_TU)  // this unit holds the DBAS family alone
-  (void)kt;
-  if (!geom || !gdb) return set_err(DTMPC_ERR_BAD_ARG, "solve backward dbas: the GEOM record and g_dbas are required");
-#define LY_LAUNCH(m, t)                                                                               \
-  do {                                                                                                \
-    if (wts) hipLaunchKernelGGL((fk::solve_backward_dbas_kernel<m, t, true>), grid, dim3(bs), 0, st, kd); \
-    else hipLaunchKernelGGL((fk::solve_backward_dbas_kernel<m, t, false>), grid, dim3(bs), 0, st, kd);    \
-  } while (0)
-  switch (sp->n_obstacles) {
-    LY_CASES
-    default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
-  }
-#undef LY_LAUNCH
-#else
-  (void)kt;
-  if (wts) {  // per-trajectory weights: one family for both record forms
-#define LY_LAUNCH(m, t)                                                                                       \
-  do {                                                                                                        \
-    if (geom) hipLaunchKernelGGL((fk::solve_backward_weights_kernel<m, t, true>), grid, dim3(bs), 0, st, kw); \
-    else hipLaunchKernelGGL((fk::solve_backward_weights_kernel<m, t, false>), grid, dim3(bs), 0, st, kw);     \
-  } while (0)
-    switch (sp->n_obstacles) {
-      LY_CASES
-      default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
-    }
-#undef LY_LAUNCH
-  } else if (!geom) {
-#define LY_LAUNCH(m, t) hipLaunchKernelGGL((fk::solve_backward_kernel<m, t>), grid, dim3(bs), 0, st, kk)
-    switch (sp->n_obstacles) {
-      LY_CASES
-      default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
-    }
-#undef LY_LAUNCH
-  } else {
-#define LY_LAUNCH(m, t) hipLaunchKernelGGL((fk::solve_backward_geom_kernel<m, t>), grid, dim3(bs), 0, st, kg)
-    switch (sp->n_obstacles) {
-      LY_CASES
-      default: return set_err(DTMPC_ERR_BAD_ARG, "solve backward: obstacle count not instantiated");
-    }
-#undef LY_LAUNCH
-  }
-#endif
-#undef LY_CASES
-#undef LY_CASE
-  return check_launch(gtg ? "solve_backward_tight_kernel" : gdb ? "solve_backward_dbas_kernel" : wts ? "solve_backward_weights_kernel"
-                      : geom ? "solve_backward_geom_kernel" : "solve_backward_kernel");
+  static_assert(std::is_standard_layout_v<fk::LKT>, "kt's address is that of the K it begins with");
+  const K& kb = reinterpret_cast<const K&>(kt);
+  const bool f = K::has_geom(false) ? o.weights != nullptr : o.geom;  // FL is W where the record is always GEOM, else G
+  const bool hit = pick_obstacles(M, [&](auto m) {
+    return pick_flag(track, [&](auto t) {
+      constexpr int Mc = decltype(m)::value;
+      constexpr bool T = decltype(t)::value;
+      if constexpr (K::kFlag) {
+        pick_flag(f, [&](auto ff) {
+          hipLaunchKernelGGL((fk::solve_backward_kernel<K, Mc, T, decltype(ff)::value>), grid, dim3(bs), 0, st, kb);
+        });
+      } else {
+        hipLaunchKernelGGL((fk::solve_backward_kernel<K, Mc, T>), grid, dim3(bs), 0, st, kb);
+      }
+    });
+  });
+  if (!hit) return not_instantiated("solve backward");
+  return check_launch(kLayerKernel[K::kVariant]);
+}
+template <class... K>
+static int launch_unit(Blocks<K...>, const fk::LKT& kt, int M, bool track, const LayerOpt& o, dim3 grid, int bs,
+                       hipStream_t st) {
+  int r = DTMPC_OK;
+  if (((K::kVariant == o.variant && ((r = launch_block<K>(kt, M, track, o, grid, bs, st)), true)) || ...)) return r;
+  return set_err(DTMPC_ERR_BAD_ARG, "solve backward: variant not in this unit");
 }
 
-// dtmpc_solve_backward and dtmpc_solve_backward_geom: the argument rules of include/dtmpc.h, then the launch
-// (dbas: dtmpc_solve_backward_dbas -- the GEOM record, g_dbas required, g_x0 / g_obs / weights each optional)
-static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
+static int launch_solve_backward(const dtmpc_spec* sp, const dtmpc_cost* cp, int64_t B, const fk::LArgs& a,
+                                 hipStream_t st, const LayerOpt& o) {
+  fk::LK kk;
+  std::memset(&kk, 0, sizeof(kk));
+  fast_p(sp, kk.p);
+  const bool track = cp->kind == DTMPC_COST_TRACK;
+  kk.c = fast_cost(*cp, track);
+  kk.a = a;
+  // the largest block: every variant's is what it begins with
+  const fk::LKG kg = {kk, (real*)o.gx0, (real*)o.gob};
+  const fk::LKW kw = {kg, (const real*)o.weights};
+  const fk::LKD kd = {kw, (real*)o.gdb};
+  const fk::LKT kt = {kd, (const real*)o.tight, (real*)o.gtg};
+  const int bs = tube_block(B, 1);
+  const dim3 grid((unsigned)((B + bs - 1) / bs));
+  return launch_unit(UnitBlocks{}, kt, sp->n_obstacles, track, o, grid, bs, st);
+}
+
+// the argument rules of include/dtmpc.h for every variant, then the launch
+static int solve_backward_entry(const LayerOpt& o, int dtype, const dtmpc_spec* spec, const dtmpc_cost* cost, int64_t B,
                                 const void* X, const void* U, const void* Xref, const void* Uref, const void* scenes,
                                 const void* gX, const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref,
-                                void* g_x0, void* g_obs, void* work, size_t work_bytes, int32_t* status,
-                                void* stream, bool wts = false, const void* weights = nullptr, bool dbas = false,
-                                void* g_dbas = nullptr, bool tightf = false, const void* tight = nullptr,
-                                void* g_tight = nullptr) {
+                                void* work, size_t work_bytes, int32_t* status, void* stream) {
   if (!spec || !cost) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL spec or cost");
   if (B < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: batch must be >= 1");
   if (spec->horizon < 1) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: horizon must be >= 1");
@@ -384,10 +334,11 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
   if (const char* why = layer_unsupported(dtype, spec, cost)) return set_err(DTMPC_ERR_BAD_ARG, why);
   if (!X || !U || !gX || !gU || !g_w || !status)
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward: NULL X, U, gX, gU, g_w or status");
-  if (wts && !weights) return set_err(DTMPC_ERR_BAD_ARG, "solve backward weights: NULL weights");
-  if (dbas && !g_dbas) return set_err(DTMPC_ERR_BAD_ARG, "solve backward dbas: NULL g_dbas");
-  if (tightf && (!tight || !g_tight)) return set_err(DTMPC_ERR_BAD_ARG, "solve backward tight: NULL tight or g_tight");
-  if (geom && !wts && !dbas && !tightf && !g_x0 && !g_obs)
+  if (o.variant == fk::kLWeights && !o.weights) return set_err(DTMPC_ERR_BAD_ARG, "solve backward weights: NULL weights");
+  if (o.variant == fk::kLDbas && !o.gdb) return set_err(DTMPC_ERR_BAD_ARG, "solve backward dbas: NULL g_dbas");
+  if (o.variant == fk::kLTight && (!o.tight || !o.gtg))
+    return set_err(DTMPC_ERR_BAD_ARG, "solve backward tight: NULL tight or g_tight");
+  if (o.variant == fk::kLGeom && !o.gx0 && !o.gob)
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward geom: g_x0 and g_obs both NULL (that is dtmpc_solve_backward)");
   if (cost->kind == DTMPC_COST_TRACK) {
     if (!Xref || !Uref) return set_err(DTMPC_ERR_BAD_ARG, "solve backward: the tracking cost needs Xref and Uref");
@@ -395,16 +346,8 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
   } else if (Xref || Uref || g_xref || g_uref) {
     return set_err(DTMPC_ERR_BAD_ARG, "solve backward: Xref, Uref, g_xref and g_uref go with the tracking cost");
   }
-  if (!work || work_bytes < layer_workspace_bytes(spec->horizon, B, geom))
-    return set_err(DTMPC_ERR_BAD_ARG, tightf ? "solve backward tight: work_bytes < "
-                                               "dtmpc_solve_backward_tight_workspace_bytes(...)"
-                                      : dbas ? "solve backward dbas: work_bytes < "
-                                             "dtmpc_solve_backward_dbas_workspace_bytes(...)"
-                                      : wts  ? "solve backward weights: work_bytes < "
-                                             "dtmpc_solve_backward_weights_workspace_bytes(...)"
-                                      : geom ? "solve backward geom: work_bytes < "
-                                             "dtmpc_solve_backward_geom_workspace_bytes(...)"
-                                           : "solve backward: work_bytes < dtmpc_solve_backward_workspace_bytes(...)");
+  if (!work || work_bytes < layer_workspace_bytes(spec->horizon, B, o.geom))
+    return set_err(DTMPC_ERR_BAD_ARG, kLayerWorkMsg[o.variant]);
   fk::LArgs a;
   a.B = (int)B;
   a.X = (const real*)X;
@@ -420,8 +363,7 @@ static int solve_backward_entry(bool geom, int dtype, const dtmpc_spec* spec, co
   a.gur = (real*)g_uref;
   a.work = (real*)work;
   a.status = status;
-  return launch_solve_backward(spec, cost, B, a, (hipStream_t)stream, geom, (real*)g_x0, (real*)g_obs,
-                               (const real*)weights, (real*)g_dbas, (const real*)tight, (real*)g_tight);
+  return launch_solve_backward(spec, cost, B, a, (hipStream_t)stream, o);
 }
 
 }  // namespace dtmpc
@@ -441,9 +383,10 @@ int dtmpc_solve_backward_tight(int dtype, const dtmpc_spec* spec, const dtmpc_co
                                void* g_target, void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* g_dbas,
                                void* g_tight, void* work, size_t work_bytes, int32_t* status, void* stream) {
   // always the GEOM record; weights == NULL is the shared cost, g_dbas == NULL leaves the DBaS sums unwritten
-  return dtmpc::solve_backward_entry(true, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
-                                     g_uref, g_x0, g_obs, work, work_bytes, status, stream, weights != nullptr, weights,
-                                     false, g_dbas, true, tight, g_tight);
+  const dtmpc::LayerOpt o = {.variant = dtmpc::fk::kLTight, .geom = true, .gx0 = g_x0, .gob = g_obs, .weights = weights,
+                             .gdb = g_dbas, .tight = tight, .gtg = g_tight};
+  return dtmpc::solve_backward_entry(o, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, work, work_bytes, status, stream);
 }
 
 #elif defined(DTMPC_FAST_LAYER_DBAS_TU)
@@ -459,9 +402,10 @@ int dtmpc_solve_backward_dbas(int dtype, const dtmpc_spec* spec, const dtmpc_cos
                               void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* g_dbas, void* work,
                               size_t work_bytes, int32_t* status, void* stream) {
   // always the GEOM record; weights == NULL is the shared cost
-  return dtmpc::solve_backward_entry(true, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
-                                     g_uref, g_x0, g_obs, work, work_bytes, status, stream, weights != nullptr, weights,
-                                     true, g_dbas);
+  const dtmpc::LayerOpt o = {.variant = dtmpc::fk::kLDbas, .geom = true, .gx0 = g_x0, .gob = g_obs, .weights = weights,
+                             .gdb = g_dbas};
+  return dtmpc::solve_backward_entry(o, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, work, work_bytes, status, stream);
 }
 
 #else
@@ -479,8 +423,9 @@ int dtmpc_solve_backward(int dtype, const dtmpc_spec* spec, const dtmpc_cost* co
                          const void* U, const void* Xref, const void* Uref, const void* scenes, const void* gX,
                          const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref, void* work,
                          size_t work_bytes, int32_t* status, void* stream) {
-  return dtmpc::solve_backward_entry(false, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
-                                     g_uref, nullptr, nullptr, work, work_bytes, status, stream);
+  const dtmpc::LayerOpt o = {.variant = dtmpc::fk::kLPlain};
+  return dtmpc::solve_backward_entry(o, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, work, work_bytes, status, stream);
 }
 
 size_t dtmpc_solve_backward_geom_workspace_bytes(int dtype, int32_t horizon, int64_t B) {
@@ -492,8 +437,9 @@ int dtmpc_solve_backward_geom(int dtype, const dtmpc_spec* spec, const dtmpc_cos
                               const void* U, const void* Xref, const void* Uref, const void* scenes, const void* gX,
                               const void* gU, void* g_w, void* g_target, void* g_xref, void* g_uref, void* g_x0,
                               void* g_obs, void* work, size_t work_bytes, int32_t* status, void* stream) {
-  return dtmpc::solve_backward_entry(true, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
-                                     g_uref, g_x0, g_obs, work, work_bytes, status, stream);
+  const dtmpc::LayerOpt o = {.variant = dtmpc::fk::kLGeom, .geom = true, .gx0 = g_x0, .gob = g_obs};
+  return dtmpc::solve_backward_entry(o, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, work, work_bytes, status, stream);
 }
 
 size_t dtmpc_solve_backward_weights_workspace_bytes(int dtype, int32_t horizon, int64_t B, int32_t geom) {
@@ -507,8 +453,10 @@ int dtmpc_solve_backward_weights(int dtype, const dtmpc_spec* spec, const dtmpc_
                                  void* g_xref, void* g_uref, void* g_x0, void* g_obs, void* work, size_t work_bytes,
                                  int32_t* status, void* stream) {
   // the GEOM record (25 values) when either of its outputs is asked for, else the plain one (20)
-  return dtmpc::solve_backward_entry(g_x0 || g_obs, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target,
-                                     g_xref, g_uref, g_x0, g_obs, work, work_bytes, status, stream, true, weights);
+  const dtmpc::LayerOpt o = {.variant = dtmpc::fk::kLWeights, .geom = g_x0 || g_obs, .gx0 = g_x0, .gob = g_obs,
+                             .weights = weights};
+  return dtmpc::solve_backward_entry(o, dtype, spec, cost, B, X, U, Xref, Uref, scenes, gX, gU, g_w, g_target, g_xref,
+                                     g_uref, work, work_bytes, status, stream);
 }
 
 #endif  // DTMPC_FAST_LAYER_DBAS_TU

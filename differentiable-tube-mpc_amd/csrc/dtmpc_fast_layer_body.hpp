@@ -1,24 +1,26 @@
-// dtmpc_fast_layer_body.hpp -- the body of solve_backward_kernel and of its GEOM variant (csrc/dtmpc_fast_layer.hip),
-// included textually into both kernels: each kernel sees `LK kk` (its argument block), a constexpr bool GEOM and, under
-// GEOM, the two further outputs gx0 / gob.  Text, not a shared device function: with GEOM false every `if constexpr
+// dtmpc_fast_layer_body.hpp -- the body of solve_backward_kernel (csrc/dtmpc_fast_layer.hip), included textually into
+// the kernel template: it sees `const LK& kk` (the LK its argument block begins with), the constexpr bools GEOM, WTS,
+// DBAS and TIGHT that the block type stands for, and the pointers gx0 / gob / wts / gdb / tgt / gtg, NULL where the
+// block has none.  Text, not a shared device function: with GEOM false every `if constexpr
 // (GEOM)` statement is discarded in the front end and the kernel's code is what it was before the variant existed
-// (a body shared through a reference to the kernel's argument compiled to other code, ten VGPRs more).
-// WTS (solve_backward_weights_kernel, dtmpc_solve_backward_weights): a third constexpr bool beside GEOM, with the
+// (a body shared through a reference to the kernel's argument compiled to other code, ten VGPRs more; so did accessors
+// that take the argument block by reference, which is why the kernel's take it by value).
+// WTS (solve_backward_kernel<LKW, ...>, dtmpc_solve_backward_weights): a third constexpr bool beside GEOM, with the
 // pointer `wts` -- the nine cost weights come from the lane's own column of the weights array [9][B] (wts_c) instead of
 // kk.c, so g_xref = -2 Q_i dx and g_target use trajectory i's own Q / Qf; with WTS false the statement is discarded.
-// DBAS (solve_backward_dbas_kernel, dtmpc_solve_backward_dbas): a fourth constexpr bool, valid with GEOM only, with the
+// DBAS (solve_backward_kernel<LKD, ...>, dtmpc_solve_backward_dbas): a fourth constexpr bool, valid with GEOM only, with the
 // pointer `gdb` [2][B] -- the rows w.r.t. alpha_eff = max(alpha, eps) and gamma: from geom_row's one evaluation of
 // h(x_m) the forward sweep also forms dBa(h) = -3 (h - a)^2 / a^4 below a (0 at and above it) and B(h) (vbarrier) and
 // keeps the sums g_alpha_eff += co_m dBa, g_gamma -= lam_{k+1} (B(h(x_k)) - b_k); row N adds its alpha term only.
 // With b_0 = B(h(x_0)) every B(h(x_k)) - b_k is zero on a rolled-out tape and the gamma row is rounding noise.  With
 // DBAS false every `if constexpr (DBAS)` statement is discarded.
-// TIGHT (solve_backward_tight_kernel, dtmpc_solve_backward_tight): a fifth constexpr bool, valid with GEOM and DBAS
+// TIGHT (solve_backward_kernel<LKT, ...>, dtmpc_solve_backward_tight): a fifth constexpr bool, valid with GEOM and DBAS
 // only, with the pointers `tgt` [B] and `gtg` [B] -- the lane's own tightening s_i goes into p.tight before the table is
 // pinned; geom_row<M, true> evaluates B' at z = h(x_m) - s_i, returns z (so dBa and B of the DBAS sums are taken at z as
 // well) and hands out co_m B'(z), which the forward sweep sums into g_tight = -sum_m co_m B'(z_m).  The backward sweep
 // k = N-1..0 is untouched: the reference linearises with B'(h) of the plain h (h_grad), so delta_lambda of a given tape
 // does not depend on s.  gdb may be NULL here.  With TIGHT false every `if constexpr (TIGHT)` statement is discarded.
-// No include guard: it is included five times on purpose.
+// No include guard: it is a function body, included once, inside the kernel template.
   static_assert(GEOM || !DBAS, "DBAS needs the GEOM record");
   static_assert(DBAS || !TIGHT, "TIGHT needs the GEOM record and the DBAS sums");
   constexpr int REC = GEOM ? kGeomRec : kLayerRec;

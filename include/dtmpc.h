@@ -506,7 +506,7 @@ int dtmpc_solve_backward_geom(int dtype, const dtmpc_spec* spec, const dtmpc_cos
  * `weights` is SoA [9][B] f32: rows Q0 Q1 Q2 R0 R1 Qf0 Qf1 Qf2 qb -- the row order of g_w -- element (row, i) at
  * row * B + i.  Trajectory i solves (and is differentiated) with the weights of column i; the dtmpc_cost passed
  * beside the array still supplies the kind, the target and wrap_angle, its nine weights are not read.  The fused f32
- * kernels read a lane's column into registers once (csrc/dtmpc_fast_weights.hip, solve_backward_weights_kernel in
+ * kernels read a lane's column into registers once (csrc/dtmpc_fast_weights.hip, solve_backward_kernel<LKW, ...> in
  * csrc/dtmpc_fast_layer.hip: 36 B more read per trajectory and phase); there is no generic-kernel or f64 form, and the
  * tube step and the receding driver take no weights array.  Added beside ABI 8. */
 
@@ -551,7 +551,7 @@ int dtmpc_solve_backward_weights(int dtype, const dtmpc_spec* spec, const dtmpc_
  * If b_0 = B(h(x_0)) then B(h(x_k)) - b_k = 0 along a rolled-out tape whatever gamma is: row 1 is zero in exact
  * arithmetic (rounding noise in f32) and is non-zero only for a solve that starts from a barrier state that is not
  * the barrier of its position (a disturbed plant state, the second of two chained solves).
- * The kernels (solve_backward_dbas_kernel, csrc/dtmpc_fast_layer_dbas.hip) are dtmpc_solve_backward_geom's with two
+ * The kernels (solve_backward_kernel<LKD, ...>, csrc/dtmpc_fast_layer_dbas.hip) are dtmpc_solve_backward_geom's with two
  * more per-lane sums formed from the evaluation of h the obstacle rows already make: the same record (100 B per step
  * and trajectory), no further workspace.  Added beside ABI 8; supported where dtmpc_solve_backward_supported says so. */
 
@@ -603,7 +603,7 @@ int dtmpc_ilqr_solve_tight(int dtype, const dtmpc_spec* spec, const dtmpc_cost* 
  * (dtmpc_ift_gradient's column DTMPC_P_TIGHT without the softplus chain, at the tape rows); the obstacle rows carry
  * B'(h - s) in place of B'(h), g_alpha_eff carries dBa(h - s) and g_gamma B(h - s) - b_k; the Riccati and sensitivity
  * sweeps keep B'(h) (see above), so delta_lambda of a given tape does not depend on s and g_x0, g_w, g_target, g_xref
- * and g_uref keep their formulas.  The kernels (solve_backward_tight_kernel, csrc/dtmpc_fast_layer_tight.hip) are
+ * and g_uref keep their formulas.  The kernels (solve_backward_kernel<LKT, ...>, csrc/dtmpc_fast_layer_tight.hip) are
  * dtmpc_solve_backward_dbas's with one more per-lane load and sum: the same record, no further workspace. */
 
 /* Scratch bytes of dtmpc_solve_backward_tight: dtmpc_solve_backward_geom_workspace_bytes' (0 as there). */

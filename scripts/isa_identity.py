@@ -2,7 +2,10 @@
 gfx950 code object is unbundled as build.py's _code_object does, disassembled with llvm-objdump -d --no-show-raw-insn
 --no-leading-addr and split per kernel; kernels are compared by their instruction text and by their metadata notes
 (register, spill and segment sizes).  Kernels present on one side only are listed, not compared.
-usage: isa_identity.py PARENT_product_objs.txt BRANCH_product_objs.txt   (build/obj/product_objs.txt of each build)"""
+--by-content UNIT[,UNIT...]: these units' kernels were renamed, so they are compared as multisets of (instruction text,
+resource notes) instead, each kernel's own symbol in its branch targets (<symbol+0x...>) replaced by a placeholder.
+usage: isa_identity.py [--by-content UNITS] PARENT_product_objs.txt BRANCH_product_objs.txt
+       (build/obj/product_objs.txt of each build)"""
 import hashlib
 import os
 import re
@@ -57,7 +60,13 @@ def unit(obj):
     return os.path.basename(obj).split(".")[0], {k: ("\n".join(v), res[k]) for k, v in code.items()}
 
 
-def main(pa, br):
+def content(kernels):
+    """The sorted multiset of a unit's kernels without their names: (sha256 of the text, resource notes)."""
+    return sorted((hashlib.sha256(text.replace(f"<{k}+", "<SELF+").encode()).hexdigest(), tuple(sorted(notes.items())))
+                  for k, (text, notes) in kernels.items())
+
+
+def main(pa, br, by_content=()):
     objs = [open(p).read().split() for p in (pa, br)]
     with ProcessPoolExecutor(max_workers=8) as pool:
         P, Q = (dict(pool.map(unit, o)) for o in objs)
@@ -65,6 +74,15 @@ def main(pa, br):
     ok = True
     for tu in sorted(P):
         a, b = P[tu], Q[tu]
+        if tu in by_content:
+            ca, cb = content(a), content(b)
+            ha, hb = (hashlib.sha256(repr([t for t, _ in c]).encode()).hexdigest()[:16] for c in (ca, cb))
+            notes = sorted(n for _, n in ca) == sorted(n for _, n in cb)
+            same = ca == cb
+            ok &= same
+            print(f"{tu:22s} {len(a):3d}/{len(b):3d}  {ha}  {hb}  {'equal' if notes else 'DIFFER'}  "
+                  f"{'IDENTICAL' if same else 'DIFFERENT'}  (by content)")
+            continue
         common = sorted(set(a) & set(b))
         ha, hb = (hashlib.sha256("\n".join(k + "\n" + s[k][0] for k in common).encode()).hexdigest()[:16] for s in (a, b))
         notes = all(a[k][1] == b[k][1] for k in common)
@@ -86,4 +104,8 @@ def main(pa, br):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    argv = sys.argv[1:]
+    units = ()
+    if argv and argv[0] == "--by-content":
+        units, argv = tuple(argv[1].split(",")), argv[2:]
+    sys.exit(main(argv[0], argv[1], units))
