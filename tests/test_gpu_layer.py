@@ -66,7 +66,8 @@ def _obstacles(M):
     base = paper_setup().problem.obstacles
     extra = (CircleObstacle(center=(2.0, 8.0), radius=0.8), CircleObstacle(center=(8.0, 8.0), radius=1.2),
              CircleObstacle(center=(8.0, 1.5), radius=0.7))
-    return {1: (CircleObstacle(center=(5.0, 5.0), radius=2.5),), 5: base, 8: base + extra}[M]
+    # M = 1: one circle in the middle of the start box; any other count: the first M of the paper's five + the extras
+    return (CircleObstacle(center=(5.0, 5.0), radius=2.5),) if M == 1 else (base + extra)[:M]
 
 
 ALPHA = 0.05  # relaxed threshold of the cases' barrier: h < ALPHA takes the quadratic extension.  (With the paper's
